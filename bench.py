@@ -8,11 +8,13 @@ smoother target are quoted on); with --gpus N the same 512³ domain is cut into 
 
 `python bench.py --gpus N` needs no launcher: it starts its N ranks itself (torch.distributed.run children, one per GPU).
 
-Prints ONE JSON line (rank 0): metric/value + `roofline` (the finest-level smoother kernel pair, HIP-event timed inside the
-timed region on the launch stream; `frac` = the kernels' OWN algorithmic bytes ÷ time ÷ 8 TB/s, `traffic_frac` = PMC bytes,
-`op_equivalent` = the reference formulation's operation bytes ÷ the same time) + `cpu_baseline` (the oracle — a CPU restatement
-of the reference algorithm, kind "port" — timed on this box's host cores on bounded samples of the same workload: all cores at
-128³ and 256³, one thread at 128³).
+Prints ONE JSON line (rank 0): metric/value/ms_per_step of the timed steps and the workload's config.  A plain run does only that:
+set up, warm up, time --steps steps (no HIP events inside them), write --dump-outputs DIR if asked, print.  With --full the line also
+carries `roofline` (the finest-level smoother kernel pair, HIP-event timed inside the timed region on the launch stream; `frac` = the
+kernels' OWN algorithmic bytes ÷ time ÷ 8 TB/s, `traffic_frac` = PMC bytes, `op_equivalent` = the reference formulation's operation
+bytes ÷ the same time), `phases_ms_per_step` (all phases with --phases) and `cpu_baseline` (the oracle — a CPU restatement of the
+reference algorithm, kind "port" — timed on this box's host cores on bounded samples of the same workload: all cores at 128³ and
+256³, one thread at 128³; --no-cpu-baseline leaves it out).
 """
 import argparse
 import ctypes as C
@@ -196,6 +198,30 @@ def build_roofline(prof, ncell, const0, kind0, N, use_traffic, xdefer=None):
     return roof
 
 
+DUMP_SAMPLE = 1 << 21      # values per field that --dump-outputs keeps (8 MiB in float32); a larger field is sampled
+
+
+def dump_outputs(sim, d):
+    """--dump-outputs DIR: what the timed path hands its caller after the last timed step, as DIR/<name>.npy.
+    u, p: the velocity and pressure fields (ghost cells included) whole, in Fortran order, where they hold at most DUMP_SAMPLE values;
+    else the values at DUMP_SAMPLE distinct flat (Fortran-order) positions drawn with a fixed seed, in increasing order: the same
+    positions for every run of the same size.
+    dt, pois_n: the Δt history and the Poisson iterations per solve, warm-up steps included (float64)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    out = {}
+    for seed, name in enumerate(("u", "p")):
+        a = sim.field(name)
+        if a.size > DUMP_SAMPLE:
+            flat = a.reshape(-1, order="F")
+            a = flat[np.sort(np.random.default_rng(seed).choice(flat.size, DUMP_SAMPLE, replace=False))]
+        out[name] = a
+    out["dt"] = np.asarray(sim.dt, dtype=np.float64)
+    out["pois_n"] = np.asarray(sim.pois_n, dtype=np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start N rank processes (one per GPU) through torch.distributed.run and relay
     their output; rank 0 prints the JSON line.  Called before this process imports torch or touches the GPU; the children are fresh
@@ -218,12 +244,21 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--size", type=int, default=512, help="interior cells per side of the TGV box")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--phases", action="store_true", help="HIP-event pairs around every phase of the step (phases_ms_per_step); the default run "
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: HIP-event timings of the roofline kernels "
+                    "inside the timed region (roofline, phases_ms_per_step) and the CPU baseline; a plain run only sets up, warms up and times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what they computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--phases", action="store_true", help="with --full: HIP-event pairs around every phase of the step (phases_ms_per_step); --full alone "
                     "only brackets the roofline kernels — each pair costs a few µs of stream time, ≈1 %% of a 512³ step with all of them on")
-    ap.add_argument("--no-phases", action="store_true", help="with WL_OPT_* switches set: keep the default (roofline kernels only) event pairs")
-    ap.add_argument("--cpu-budget", type=float, default=12.0)
+    ap.add_argument("--no-phases", action="store_true", help="with --full and WL_OPT_* switches set: keep the default (roofline kernels only) event pairs")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="with --full: seconds per leg of the CPU baseline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.phases and not args.full:
+        ap.error("--phases is a --full measurement: add --full")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs is implemented for --gpus 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -263,8 +298,8 @@ def main():
     N = args.size
     if world > 1:
         from waterlily_jl_amd import slab
-        return slab.bench_main(args, world, rank, local_rank, read_prof=read_prof, build_roofline=build_roofline,
-                               cpu_baseline=None if args.no_cpu_baseline else (lambda: cpu_baseline(budget_s=args.cpu_budget)))
+        return slab.bench_main(args, world, rank, local_rank, read_prof=read_prof if args.full else None, build_roofline=build_roofline,
+                               cpu_baseline=None if (args.no_cpu_baseline or not args.full) else (lambda: cpu_baseline(budget_s=args.cpu_budget)))
 
     sim = w.FusedSimulation((N, N, N), (0, 0, 0), N, U=1, nu=N / 1600.0, ic="tgv")
     import ctypes as C
@@ -277,8 +312,9 @@ def main():
     sim.mom_steps_(args.warmup)      # wl_sim_mom_steps: the K steps of the timed region are ONE library call too (same results as K calls of wl_sim_mom_step)
     sim.sync()
     n_warm = len(sim.pois_n)
-    all_phases = args.phases or (any(k.startswith("WL_OPT_") for k in os.environ) and not args.no_phases)
-    check(lib.wl_prof_enable(1 if all_phases else 2))
+    if args.full:
+        all_phases = args.phases or (any(k.startswith("WL_OPT_") for k in os.environ) and not args.no_phases)
+        check(lib.wl_prof_enable(1 if all_phases else 2))
     def counter(name):
         v = C.c_long()
         check(lib.wl_sim_counter(sim._h, name.encode(), C.byref(v)))
@@ -290,11 +326,13 @@ def main():
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     launches_per_step = (int(lib.wl_launch_count()) - l0) / args.steps
-    prof = read_prof(lib)
-    check(lib.wl_prof_enable(0))
+    if args.full:
+        prof = read_prof(lib)
+        check(lib.wl_prof_enable(0))
+    if args.dump_outputs:
+        dump_outputs(sim, args.dump_outputs)
     ncell = float(N) ** 3
     pn = sim.pois_n[n_warm:]
-    roof = build_roofline(prof, ncell, bool(sim.const_levels()[0]), sim.smoother_kinds()[0], N, use_traffic=True, xdefer=counter("xdefer"))
     out = {
         "metric": "cells*steps/sec (3D TGV) ; smoother HBM GB/s vs peak", "value": ncell * args.steps / el, "unit": "cells*steps/s",
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3, "higher_is_better": True,
@@ -304,11 +342,12 @@ def main():
                    "constant_coefficient_levels": sim.const_levels(), "smoother_kinds": sim.smoother_kinds(),
                    # kernel launches per mom_step! in the timed region; solves whose fused projection head stood / had to be redone (residual!'s mean shift due)
                    "placement_trial_ms": placement, "launches_per_step": launches_per_step, "resjac": counter("resjac") - rj0, "resjac_redo": counter("resjac_redo") - rd0},
-        "roofline": roof,
-        "phases_ms_per_step": {k: (v["total_ms"] / args.steps) for k, v in prof.items() if v["launches"]},
     }
-    if not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(budget_s=args.cpu_budget)
+    if args.full:
+        out["roofline"] = build_roofline(prof, ncell, bool(sim.const_levels()[0]), sim.smoother_kinds()[0], N, use_traffic=True, xdefer=counter("xdefer"))
+        out["phases_ms_per_step"] = {k: (v["total_ms"] / args.steps) for k, v in prof.items() if v["launches"]}
+        if not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(budget_s=args.cpu_budget)
     print(json.dumps(out))
 
 

@@ -1,5 +1,6 @@
-"""bench.py's driver contract: `python bench.py --gpus N` starts N ranks by itself (no launcher), the roofline block uses the kernels'
-own bytes for `frac`, and the PMC traffic figure is only quoted for the kernel sources it was measured on."""
+"""bench.py's driver contract: `python bench.py --gpus N` starts N ranks by itself (no launcher), a plain run times --steps steps and
+prints the headline only (--dump-outputs DIR: what those steps computed), --full adds the roofline block, which uses the kernels' own
+bytes for `frac` and quotes the PMC traffic figure only for the kernel sources it was measured on, and the CPU baseline."""
 import json
 import os
 import subprocess
@@ -39,6 +40,12 @@ def test_no_gpu_is_a_loud_error():
         pytest.skip("a GPU is present")
     r, line = run_bench("--steps", "1", "--warmup", "0")
     assert r.returncode != 0 and line is None and "no CPU fallback" in (r.stderr + r.stdout)
+
+
+def test_options_that_need_full_or_one_gpu_are_refused():
+    for args, msg in ((("--phases",), "--full"), (("--gpus", "2", "--dump-outputs", "x"), "--gpus 1"), (("--steps", "0"), "--steps")):
+        r, line = run_bench(*args, env={"WL_BENCH_DRY": "1"})
+        assert r.returncode != 0 and line is None and msg in r.stderr, (args, r.stderr[-2000:])
 
 
 def _fake_prof(a_ms, b_ms):
@@ -85,7 +92,7 @@ def test_roofline_frac_is_own_bytes_not_operation_bytes(tmp_path, monkeypatch):
 
 @pytest.mark.gpu
 def test_two_rank_rehearsal_on_one_gpu_prints_n_gpus_2():
-    r, line = run_bench("--gpus", "2", "--size", "128", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    r, line = run_bench("--gpus", "2", "--size", "128", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
                         env={"WL_BENCH_ONE_GPU": "1", "WL_DIST_BACKEND": "gloo"}, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert line["n_gpus"] == 2 and line["config"]["transport"] == "CallbackComm" and line["value"] > 0
@@ -94,9 +101,9 @@ def test_two_rank_rehearsal_on_one_gpu_prints_n_gpus_2():
 
 @pytest.mark.gpu
 def test_single_gpu_line_carries_roofline_probe_and_cpu_baseline():
-    """the default single-GPU line at a small size: the contract keys, the roofline on the kernels' own bytes, launch and path counters, and the CPU
+    """the --full single-GPU line at a small size: the contract keys, the roofline on the kernels' own bytes, launch and path counters, and the CPU
     baseline (port) with its serial companion"""
-    r, line = run_bench("--size", "128", "--steps", "5", "--warmup", "2", "--cpu-budget", "3", timeout=900)
+    r, line = run_bench("--size", "128", "--steps", "5", "--warmup", "2", "--full", "--cpu-budget", "3", timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in line, k
@@ -108,3 +115,53 @@ def test_single_gpu_line_carries_roofline_probe_and_cpu_baseline():
     assert cfg["launches_per_step"] > 10 and cfg["resjac"] + cfg["resjac_redo"] >= 0 and cfg["mean_pois_n"] >= 1
     cb = line["cpu_baseline"]
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and cb["serial"]["cores"] == 1
+
+
+HEADLINE_KEYS = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
+
+
+@pytest.mark.gpu
+def test_plain_line_is_lean_and_dumps_what_the_timed_steps_computed(tmp_path):
+    """a plain run (no --full): the headline keys and none of the measurements --full adds; --steps sets the timed steps; --dump-outputs
+    writes the fields the timed path left after its last step, bit for bit what the same steps give through the library directly"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import waterlily_jl_amd as w
+    n, warm, steps = 64, 2, 3
+    r, line = run_bench("--size", str(n), "--steps", str(steps), "--warmup", str(warm), "--dump-outputs", str(tmp_path), timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    for k in HEADLINE_KEYS:
+        assert k in line, k
+    assert line["steps"] == steps and line["warmup"] == warm and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert not {"roofline", "phases_ms_per_step", "cpu_baseline"} & set(line)
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 - n**3) < 1e-9 * n**3      # value = cells·steps / s over the timed steps
+    got = {k: np.load(tmp_path / f"{k}.npy") for k in ("u", "p", "dt", "pois_n")}
+    assert sorted(os.listdir(tmp_path)) == ["dt.npy", "p.npy", "pois_n.npy", "u.npy"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    w.core.device()
+    s = w.FusedSimulation((n, n, n), (0, 0, 0), n, U=1, nu=n / 1600.0, ic="tgv")
+    s.mom_steps_(warm)
+    s.mom_steps_(steps)
+    assert got["u"].shape == (n + 2,) * 3 + (3,) and np.array_equal(got["u"], s.field("u")) and np.array_equal(got["p"], s.field("p"))
+    assert len(got["dt"]) == 1 + warm + steps and got["dt"].tolist() == [float(v) for v in s.dt]
+    assert len(got["pois_n"]) == 2 * (warm + steps) and got["pois_n"].tolist() == s.pois_n
+
+
+@pytest.mark.gpu
+def test_dump_outputs_samples_large_fields_at_the_same_positions_every_run(tmp_path):
+    """fields larger than DUMP_SAMPLE values are written as a fixed seeded sample: two runs of the same arguments write the same files"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    runs = []
+    for d in ("a", "b"):
+        r, line = run_bench("--size", "128", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / d), timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        assert line["steps"] == 2 and "roofline" not in line
+        runs.append({k: np.load(tmp_path / d / f"{k}.npy") for k in ("u", "p", "dt", "pois_n")})
+    a, b = runs
+    assert a["u"].shape == a["p"].shape == (bench.DUMP_SAMPLE,) and a["u"].dtype == a["p"].dtype == np.float32
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < 64 << 20
+    assert np.isfinite(a["u"]).all() and np.abs(a["u"]).max() > 0.1
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k

@@ -1,8 +1,10 @@
 """The Julia binding (waterlily.jl_amd/julia/WaterLilyHIPExt.jl) cannot run here — no Julia exists in this image or on the GPU box.
 What can be checked without Julia is checked:
  1. sites.json lists EVERY `@loop` / `@inside` / broadcast / reduction / array-constructor site of the reference files that
-    Simulation(...) + sim_step! (+ the force read-outs) reach; this test re-scans /root/reference/src and fails on any site that is not
-    listed (or whose line moved) — skipped where the reference is absent (GPU box);
+    Simulation(...) + sim_step! (+ the force read-outs) reach; this test holds it against the scan of the reference's src/ recorded in
+    tests/golden/reference_sites.json (file, line and a hash of the text of every site; tests/golden/make_reference_sites.py makes it)
+    and fails on any site that is not listed (or whose line moved); with WATERLILY_JL_SRC naming the reference's src/ directory it
+    re-scans the reference and checks the recording first;
  2. every listed site names the method of the binding that intercepts it, and that method's signature is present in the file;
  3. every `ccall` of the binding names a symbol include/wlhip.h declares, with the declared number of arguments;
  4. the Julia mirrors of the C structs (WlGrid, WlBody, WlSimDesc) have the fields of include/wlhip.h in order;
@@ -10,17 +12,37 @@ What can be checked without Julia is checked:
     that is ambiguous with Base's broadcast-style rules, no dictionary keyed by a device array (hashing = scalar getindex per element),
     no per-step path through scalar getindex, the spare velocity array handed over for every flow, uniform closures kept on the composite.
 The call SEQUENCE the binding performs for the composite time step is executed, through ctypes, by tests/test_gpu_callerowned.py."""
+import hashlib
 import json
 import os
 import re
 
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 JL = os.path.join(ROOT, "waterlily.jl_amd", "julia", "WaterLilyHIPExt.jl")
 SITES = os.path.join(ROOT, "waterlily.jl_amd", "julia", "sites.json")
-REF = "/root/reference/src"
+REF_SITES = os.path.join(ROOT, "tests", "golden", "reference_sites.json")
 PAT = re.compile(r'@loop|@inside|\.=|\.\*=|\./=|\.\+=|\.-=|\bsum\(|\bmaximum\(|⋅|\bfill!\(|\bcopy\(|\bsimilar\(')
+REF_FILES = ("core.jl", "Flow.jl", "Poisson.jl", "MultiLevelPoisson.jl", "Body.jl", "WaterLily.jl", "Metrics.jl")
+
+
+def text_hash(text):
+    return hashlib.sha256(text.encode("utf-8")).hexdigest()[:16]
+
+
+def scan_reference(src, scope):
+    """[file, line, hash of the line's first 110 stripped characters] of every site of the reference's src/ directory, in file order"""
+    scope = {k: [tuple(r) for r in v] for k, v in scope.items()}
+    found = []
+    for f in REF_FILES:
+        for i, line in enumerate(open(os.path.join(src, f), encoding="utf-8").read().split("\n"), 1):
+            st = line.strip()
+            if f in scope and not any(a <= i <= b for a, b in scope[f]):
+                continue
+            if not PAT.search(line) or st.startswith("#"):
+                continue
+            found.append(["src/" + f, i, text_hash(st[:110])])
+    return found
 
 
 def test_every_listed_site_has_an_interceptor_in_the_binding():
@@ -44,24 +66,19 @@ def test_every_listed_site_has_an_interceptor_in_the_binding():
     assert "KernelAbstractions.get_backend(::HipArray)" in src and "apply!(f, c::HipArray{T,N})" in src
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference is not present on this machine")
 def test_site_list_is_complete_and_current_against_the_reference():
     j = json.load(open(SITES, encoding="utf-8"))
+    rec = json.load(open(REF_SITES, encoding="utf-8"))
+    assert rec["pattern"] == PAT.pattern and rec["scope"] == j["scope"], "the recorded scan was made with another pattern or scope"
+    src = os.environ.get("WATERLILY_JL_SRC")
+    if src:
+        assert scan_reference(src, j["scope"]) == rec["sites"], "the reference differs from the recorded scan: rerun tests/golden/make_reference_sites.py"
     listed = {(s["file"], s["line"]): s for s in j["sites"]}
-    scope = {k: [tuple(r) for r in v] for k, v in j["scope"].items()}
-    found = set()
-    for f in ("core.jl", "Flow.jl", "Poisson.jl", "MultiLevelPoisson.jl", "Body.jl", "WaterLily.jl", "Metrics.jl"):
-        for i, line in enumerate(open(os.path.join(REF, f), encoding="utf-8").read().split("\n"), 1):
-            st = line.strip()
-            if f in scope and not any(a <= i <= b for a, b in scope[f]):
-                continue
-            if not PAT.search(line) or st.startswith("#"):
-                continue
-            key = ("src/" + f, i)
-            found.add(key)
-            assert key in listed, f"unlisted site {key}: {st}"
-            assert listed[key]["text"] == st[:110], f"{key}: the reference line changed"
-    assert found == set(listed), sorted(set(listed) - found)
+    found = {(f, i): h for f, i, h in rec["sites"]}
+    for key, h in found.items():
+        assert key in listed, f"unlisted site {key}"
+        assert text_hash(listed[key]["text"]) == h, f"{key}: the reference line changed"
+    assert set(found) == set(listed), sorted(set(listed) - set(found))
 
 
 def _header_decls():

@@ -1,9 +1,10 @@
 #!/bin/bash
 # usage: tools/rj_chunks.sh [SIZE] — number of z-chunks of the fused projection head (WL_RJ_CHUNKS), ms per step of the head (both solves)
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"      # the bench lines and their stderr
 SIZE=${1:-512}
-run() { python bench.py --phases --steps 8 --warmup 3 --size $SIZE --no-cpu-baseline > gpurun_out/cg.json 2> gpurun_out/cg.err; python - <<PY
+run() { python bench.py --full --phases --steps 8 --warmup 3 --size $SIZE --no-cpu-baseline > $OUT/cg.json 2> $OUT/cg.err; python - <<PY
 import json
-j=json.loads(open("gpurun_out/cg.json").read().strip().splitlines()[-1]); p=j["phases_ms_per_step"]
+j=json.loads(open("$OUT/cg.json").read().strip().splitlines()[-1]); p=j["phases_ms_per_step"]
 print("$SIZE", "$1", "step", round(j["ms_per_step"],3), "head", round(p.get("residual",0),3))
 PY
 }

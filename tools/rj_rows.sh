@@ -1,8 +1,9 @@
 #!/bin/bash
 # usage: tools/rj_rows.sh — tile height of the fused projection head (WL_RJ_ROWS=16|32) at several sizes: ms per step, head (both solves)
-run() { name=$1; shift; env "$@" python bench.py --phases --steps ${STEPS} --warmup 3 --size $SIZE --no-cpu-baseline > gpurun_out/cg.json 2> gpurun_out/cg.err; python - <<PY
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"      # the bench lines and their stderr
+run() { name=$1; shift; env "$@" python bench.py --full --phases --steps ${STEPS} --warmup 3 --size $SIZE --no-cpu-baseline > $OUT/cg.json 2> $OUT/cg.err; python - <<PY
 import json
-j=json.loads(open("gpurun_out/cg.json").read().strip().splitlines()[-1]); p=j["phases_ms_per_step"]
+j=json.loads(open("$OUT/cg.json").read().strip().splitlines()[-1]); p=j["phases_ms_per_step"]
 print("$SIZE", "$name", "step", round(j["ms_per_step"],3), "head", round(p.get("residual",0),3))
 PY
 }
