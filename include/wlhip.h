@@ -149,6 +149,8 @@ int wl_mg_solve(wl_mg* mg, double tol, int itmx, int* host_n, double* host_r1, f
 int wl_mg_history(const wl_mg* mg, int16_t* host_out, int cap);                        /* pois.n :66 */
 /* per-iteration log of the last solve: what `@log` prints (:112,117): r∞, r₁, ω */
 int wl_mg_last_log(const wl_mg* mg, double* host_r1, double* host_rinf, double* host_omega, int cap);
+/* how the last solve applied residual!'s mean shift (:95-97): 0 a pass of its own, 1 inside the finest level's z-marching Jacobi!, 2 the fused projection head; -1 no solve yet */
+int wl_mg_shift_path(const wl_mg* mg);
 
 /* ---- Simulation/Flow composite (what bench.py times): src/Flow.jl:156-167, src/WaterLily.jl:128-139 */
 typedef struct wl_sim wl_sim;

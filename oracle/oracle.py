@@ -88,6 +88,7 @@ def lib(omp=False):
                                         C.c_int, IC_FN, C.c_int, C.c_void_p, dbl, BC_FN, C.c_void_p]),
         ("wlo_sim_destroy", None, [C.c_void_p]),
         ("wlo_sim_field", C.c_void_p, [C.c_void_p, C.c_char_p]),
+        ("wlo_sim_set_itmx", None, [C.c_void_p, C.c_int]),
         ("wlo_sim_step", None, [C.c_void_p, C.c_int]),
         ("wlo_sim_step_until", C.c_int, [C.c_void_p, dbl, C.c_int, C.c_int]),
         ("wlo_sim_measure", None, [C.c_void_p]),
@@ -476,7 +477,7 @@ class Simulation:
     """
 
     def __init__(self, dims, uBC, L, U=None, dt=0.25, nu=0.0, eps=1.0, g=None, u0=None, perdir=(), exitBC=False,
-                 scheme=QUICK, body=None, T=np.float32, duBC_dt=None, omp=False):
+                 scheme=QUICK, body=None, T=np.float32, duBC_dt=None, omp=False, itmx=32):
         self._lib = lib(omp)
         self.D = len(dims)
         self.dims = tuple(int(n) for n in dims)
@@ -511,6 +512,7 @@ class Simulation:
                                           perdir_mask(perdir), int(exitBC), scheme, icfn, kind, c, R, gfn, None)
         if not self.h:
             raise AssertionError(self._lib.wlo_last_error().decode())
+        self._lib.wlo_sim_set_itmx(self.h, int(itmx))      # solver!'s cap in mom_project! (src/MultiLevelPoisson.jl:108)
         if body is not None and (body[0] != "sphere" or len(body) > 3):
             self.set_body(body)      # the constructor's measure! only knows the sphere: redo it with the full description
             self.measure()

@@ -674,6 +674,7 @@ struct Flow {
   UBC<T, D> uBC;
   UBC<T, D> g; bool has_g = false;
   std::vector<T> dt;
+  int itmx = 32;       // solver!'s cap inside mom_project! (src/MultiLevelPoisson.jl:108)
   T nu = 0;
   bool exitBC_ = false;
   PerDir perdir;
@@ -732,7 +733,7 @@ struct Flow {
     T dtl = w * dt.back();
     for_box<D>(inside<D>(Ng), [&](const CI<D>& I) { p0.z(I) = divu<T, D>(I, u); });
     for (long k = 0; k < p0.x.len(); k++) p0.x.p[k] *= dtl;
-    b.solve();
+    b.solve(2e-3, itmx);
     for (int i = 1; i <= D; i++)
       for_box<D>(inside<D>(Ng), [&](const CI<D>& I) { u(I, i) -= p0.L(I, i) * d_scalar<T, D>(i, I, p0.x); });
     for (long k = 0; k < p0.x.len(); k++) p0.x.p[k] /= dtl;

@@ -288,6 +288,7 @@ void* wlo_sim_field(void* h, const char* name) {
   });
   return out;
 }
+void wlo_sim_set_itmx(void* h, int itmx) { SIM(h, sim->flow.itmx = itmx); }   // solver!'s cap inside mom_project! (default 32)
 void wlo_sim_step(void* h, int remeasure) { SIM(h, sim->step(remeasure != 0)); }
 int wlo_sim_step_until(void* h, double t_end, int remeasure, int max_steps) { int n = 0; SIM(h, n = sim->step_until(t_end, remeasure != 0, max_steps)); return n; }
 void wlo_sim_measure(void* h) { SIM(h, sim->measure()); }

@@ -109,6 +109,7 @@ SIGNATURES = {
     "wl_mg_solve": (i32, [P, f64, i32, C.POINTER(i32), C.POINTER(f64), C.POINTER(f32), P]),
     "wl_mg_history": (i32, [P, C.POINTER(C.c_int16), i32]),
     "wl_mg_last_log": (i32, [P, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), i32]),
+    "wl_mg_shift_path": (i32, [P]),
     "wl_sim_create": (i32, [C.POINTER(P), C.POINTER(wl_sim_desc)]),
     "wl_sim_create_on": (i32, [C.POINTER(P), C.POINTER(wl_sim_desc), P]),
     "wl_sim_destroy": (i32, [P]),

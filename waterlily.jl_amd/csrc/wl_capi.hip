@@ -415,6 +415,7 @@ int wl_mg::solve(double tol, int itmx, int* host_n, double* host_r1, float* host
     // (always run: nᵖ ≥ 1): that kernel applies the shift as it loads r and accumulates the norms, no pass over r at all
     shift_pending = !jacobi0_done && defer_shift && itmx >= 1 && !(comm && comm->size > 1) && !perdir && lv.size() > 1 && wl::jacobi_takes_shift(p.x_, p.cl);
     if (!shift_pending && !jacobi0_done) WL_TRY(wl::shift_norms_dev(p.r, p.x_, ws, 1, 0, s));
+    shift_path = jacobi0_done ? 2 : (shift_pending ? 1 : 0);
   }
   double hd[8]; float hf[8];
   float w = 1.f;
@@ -424,8 +425,8 @@ int wl_mg::solve(double tol, int itmx, int* host_n, double* host_r1, float* host
   log_r1.clear(); log_rinf.clear(); log_w.clear();
   if (jacobi0_done && pre_r1 && pre_rinf) { r1 = (float)*pre_r1; log_r1.push_back(*pre_r1); log_rinf.push_back((double)*pre_rinf); log_w.push_back(1.0); have_r1 = true; }
   std::function<int(const float*)> tail; tail.swap(spec_tail);     // one-shot
-  const bool check_head = spec_check_head; spec_check_head = false;
-  tail_stood = false;
+  const int check_head = spec_check_head; spec_check_head = 0;
+  tail_stood = head_decided = head_due = false;
   while (np < itmx) {
     WL_TRY(vcycle(0, w, s, true));
     bool nd = false;
@@ -435,7 +436,7 @@ int wl_mg::solve(double tol, int itmx, int* host_n, double* host_r1, float* host
     WL_TRY(wl::combine_results(comm, ws, s));                                             // (slot 0 becomes P·Σr: not used again)
     const bool spec = (bool)tail && norm_slots == 0 && !comm;
     if (spec) {   // the break test on the device, and the projection tail behind it: runs iff this iteration is the last one
-      WL_TRY(wl::decide_converged(ws, r1tol, rinftol, (double)wl_ninside_global(p.g), (check_head && np == 0) ? 1 : 0, 2, 1, 4, s));
+      WL_TRY(wl::decide_converged(ws, r1tol, rinftol, (double)wl_ninside_global(p.g), np == 0 ? check_head : 0, 2, 1, 4, s));
       if (!ev_decided) WL_HIP(hipEventCreateWithFlags(&ev_decided, hipEventDisableTiming));
       const float* go = ws.res_f + 4;
       WL_TRY(wl::read_results_overlapped(ws, hd, 7, hf, 5, s, ev_decided, [&]() -> int { return tail(go); }));   // the copy of the norms sits between the decision and the tail: the host wakes for the copy and goes on queueing work behind the running tail
@@ -455,10 +456,10 @@ int wl_mg::solve(double tol, int itmx, int* host_n, double* host_r1, float* host
     else if (rnew < r1) w = (float)std::fmin(1.0, 1.02 * (double)w);                      // :120-121
     r1 = rnew;
     if (spec) {
-      // the device's flag IS the decision (same statements as below on the same two numbers; with check_head also the head's mean-shift test — if that one failed
-      // the caller discards this solve: stop here, the tail has not run)
-      if (check_head && np == 1 && !(std::fabs((float)hd[0] / (float)(double)wl_ninside_global(p.g)) <= 2.f * 1.1920929e-7f)) break;
-      if (hf[4] != 0.f) { tail_stood = true; break; }
+      // the device's flag IS the decision (same statements as below on the same two numbers; with check_head, first the head's mean-shift test — −1: the
+      // caller discards this solve, stop here, the tail has not run)
+      if (check_head && np == 1) { head_decided = true; if (hf[4] < 0.f) { head_due = true; break; } }
+      if (hf[4] > 0.f) { tail_stood = true; break; }
       continue;
     }
     if ((double)r1 < r1tol && (double)rinf < rinftol) break;
@@ -676,6 +677,7 @@ int wl_mg_set_fused(wl_mg* mg, int on) { mg->use_fused = (on & 1) != 0; mg->stor
 int wl_mg_vcycle(wl_mg* mg, int l, float w, void* st) { WL_CHECK(l >= 0 && l + 1 < (int)mg->lv.size(), "level out of range"); return mg->vcycle(l, w, wl_stream(st), false); }
 int wl_mg_solve(wl_mg* mg, double tol, int itmx, int* n, double* r1, float* rinf, void* st) { return mg->solve(tol, itmx <= 0 ? 32 : itmx, n, r1, rinf, wl_stream(st)); }
 int wl_mg_history(const wl_mg* mg, int16_t* out, int cap) { const int n = (int)mg->n.size(); for (int k = 0; k < n && k < cap; k++) out[k] = mg->n[(size_t)k]; return n; }
+int wl_mg_shift_path(const wl_mg* mg) { return mg->shift_path; }
 int wl_mg_last_log(const wl_mg* mg, double* r1, double* rinf, double* w, int cap) {
   const int n = (int)mg->log_r1.size();
   for (int k = 0; k < n && k < cap; k++) { r1[k] = mg->log_r1[(size_t)k]; rinf[k] = mg->log_rinf[(size_t)k]; w[k] = mg->log_w[(size_t)k]; }

@@ -72,6 +72,10 @@ static inline long wl_ncell(const wl_grid& g) { return (long)g.nx * g.ny * g.nz;
 // number of interior cells owned by this rank
 static inline long wl_ninside_local(const wl_grid& g) { return (long)(g.nx - 2) * (g.ny - 2) * (g.D == 3 ? (g.k1 - g.k0) : 1); }
 static inline long wl_ninside_global(const wl_grid& g) { return (long)(g.nx - 2) * (g.ny - 2) * (g.D == 3 ? (g.gnz - 2) : 1); }
+// residual!'s mean shift is due: |Σr/N| > 2eps(Float32)   src/Poisson.jl:95-97.  Julia sums r in Float32 (pairwise); the kernels sum in Float64 and round
+// that to Float32 first.  The one statement of the predicate: every kernel that shifts r and every host decision about the fused head evaluate it here.
+__host__ __device__ inline float wl_shift_mean(double sum, double n_inside) { return (float)sum / (float)n_inside; }
+__host__ __device__ inline bool wl_shift_due(double sum, double n_inside) { return !(fabsf(wl_shift_mean(sum, n_inside)) <= 2.f * 1.1920929e-7f); }
 
 // Launch geometry: 1-D grid; threads run linearly over an x-y plane (perfectly coalesced, ghosts masked).
 // XCD-aware block->tile map: the 8 XCDs of MI355X have private L2s and workgroups are dealt to them
@@ -206,7 +210,7 @@ struct BcFold { int on; float U[3];
                 const float* proj_x = nullptr; int proj_done = 0;
                 // in: BC!(u_in,U) was deferred — the producer of u_in wrote the interior only (wl_sim, mom_step!): the tail reads the wall-normal boundary faces as U
                 int usub = 0;
-                // in: device flag — the tail kernel does nothing unless *go != 0 (the solver's convergence decision taken on the device: wl::decide_converged; the tail is
+                // in: device flag — the tail kernel does nothing unless *go > 0 (the solver's convergence decision taken on the device: wl::decide_converged; the tail is
                 // queued behind the V-cycle before the host has read the norms)
                 const float* go = nullptr;
                 // in (conv_diff!+BDIM! launches): Δt is read from this device location instead of the argument (wl_sim_mom_steps: the next step's predictor is queued
@@ -305,7 +309,7 @@ int resjac(float* xout, float* rout, const float* x, const float* u, const GridX
            bool shell = true, const float* bcU = nullptr);   // shell = false: x's (and x_out's) ghost cells are known to be +0 — the ghost-shell scaling pass is skipped
 int shell_nonzero(const float* a, const GridX& g, int* dev_flag, hipStream_t s);
 int project_unscale(float* u, const float* L, const float* x, float* pout, const GridX& g, float dt, const ConstL& cl, hipStream_t s, const BcFold* fold = nullptr);
-int decide_converged(const RedWs& ws, double r1tol, double rinftol, double ninside, int check_head, int slot_d, int slot_f, int out_slot, hipStream_t s);   // res_f[out_slot] = 1/0: solver!'s break test (and the fused head's mean-shift test) on the device
+int decide_converged(const RedWs& ws, double r1tol, double rinftol, double ninside, int check_head, int slot_d, int slot_f, int out_slot, hipStream_t s);   // res_f[out_slot] = 1 converged / 0 iterate / −1 the fused head's mean shift is due: solver!'s break test on the device
 bool project_cfl_pair_path(const GridX& g, const ConstL& cl);   // the two-cells-per-thread tail will run (the form that honours BcFold::usub)
 int project_cfl(float* uout, const float* uin, const float* L, const float* x, float* pout, float* sigma, const GridX& g, float dt, const ConstL& cl, const RedWs& ws, int slot_f, hipStream_t s, int store_sigma = 1, const BcFold* fold = nullptr);
 int project_unscale_split(float* u, const float* L, const float* x, float* pout, const GridX& g, float dt, const ConstL& near, const ConstL& far, int na, int nb, hipStream_t s);

@@ -34,8 +34,12 @@ struct wl_mg {
   bool deep_halo = true;     // z-slabs with >= 5 ghost planes: one r exchange (5 planes) per smooth! instead of r (2) + ϵ_mid (3) + r' (2)
   // One-shot hook of the next solve(): the projection tail, queued behind every iteration's smoother BEFORE the host reads that iteration's norms and gated on the
   // device by the break test (wl::decide_converged → res_f[4], also the host's decision): no idle GPU while the host decides, nothing happens if the loop goes on.
-  // spec_check_head: the flag of the first iteration also requires the fused head's mean-shift test to pass (wl_sim's early V-cycle).  tail_stood: the tail ran.
-  std::function<int(const float*)> spec_tail; bool spec_check_head = false, tail_stood = false;
+  // spec_check_head: 1 — the flag of the first iteration first carries the fused head's mean-shift test (wl_sim's early V-cycle), 2 — declares that shift due
+  // (test hook).  Results: tail_stood — the tail ran; head_decided — the device took the head's decision, head_due — and found the shift due (the loop stopped
+  // after that iteration: the caller discards the solve).
+  std::function<int(const float*)> spec_tail; int spec_check_head = 0; bool tail_stood = false, head_decided = false, head_due = false;
+  int shift_path = -1;      // how the last solve applied residual!'s mean shift (src/Poisson.jl:95-97): 0 its own pass (k_shift_norms), 1 inside the finest level's
+                            // z-marching Jacobi! (deferred), 2 left to the caller (the fused projection head); −1 no solve yet
   hipStream_t side = nullptr; hipEvent_t ev_decided = nullptr;   // the host waits for the copy of such an iteration's norms (this event), not for the tail queued behind it
   double first_hd0 = 0.0;   // res_d[0] as the first iteration's read found it (the fused head's Σr when its check is deferred: wl_sim)
   bool jacobi0_done = false; // the fused projection head (wl_resjac.hip) already ran the V-cycle's first Jacobi! on the finest level and left solver!'s first norms

@@ -143,7 +143,7 @@ __device__ __forceinline__ float wl_dec_f(int k) { return __int_as_float(k >= 0 
 template <int D, int CL>
 __global__ void k_project_unscale(GridX g, float* __restrict__ u, const float* __restrict__ L, const float* __restrict__ x, float* __restrict__ pout, float dt, wl::ConstL cl, int zchunk,
                                   int p0, int p1, BcFold bc, int lin) {   // local planes [p0,p1) of this launch; bc.on: BC!(u,U) folded into the stores (wl_bcfold.hpp); lin: linear block order (wl_tile_lin)
-  if (bc.go && *bc.go == 0.f) return;      // queued before the host knew whether the solve had converged: it had not
+  if (bc.go && !(*bc.go > 0.f)) return;   // queued before the host knew whether the solve had converged: it had not (0), or the solve is discarded (−1)
   int i, j; long m; int pz;
   if (lin) wl_tile_lin(g, m, pz); else wl_tile(g, m, pz);
   if (!cell_ij(g, m, i, j)) return;
@@ -252,7 +252,7 @@ __device__ __forceinline__ bool pl_pair(const GridX& g, long& m, int& k, int p0)
 static inline unsigned pl_grid(const GridX& g, int nplanes) { const long np2 = (g.sz / 2 + WL_BLOCK - 1) / WL_BLOCK; return (unsigned)((((np2 + 7) >> 3) << 3) * nplanes); }
 __global__ void __launch_bounds__(WL_BLOCK) k_project_unscale2(GridX g, float* __restrict__ u, const float* __restrict__ x, float* __restrict__ pout, float dt, wl::ConstL cl,
                                                                   int p0, int p1, BcFold bc) {
-  if (bc.go && *bc.go == 0.f) return;
+  if (bc.go && !(*bc.go > 0.f)) return;
   long m; int k;
   if (!pl_pair(g, m, k, p0) || k >= p1) return;
   const int j = (int)(m / g.nx), i0 = (int)(m - (long)j * g.nx);
@@ -280,7 +280,7 @@ __global__ void __launch_bounds__(WL_BLOCK) k_project_unscale2(GridX g, float* _
 __global__ void __launch_bounds__(WL_BLOCK) k_project_cfl2(GridX g, float* __restrict__ uout, const float* __restrict__ uin, const float* __restrict__ x, float* __restrict__ pout,
                                                               float* __restrict__ sigma, float dt, wl::ConstL cl, int kfirst, int klast, float* __restrict__ pmax, int p0, int p1,
                                                               int store_sigma, BcFold bc) {
-  if (bc.go && *bc.go == 0.f) return;      // (block-uniform; the maximum's slots keep k_enc_init's −∞)
+  if (bc.go && !(*bc.go > 0.f)) return;   // (block-uniform; the maximum's slots keep k_enc_init's −∞)
   long m; int k;
   float mx = -INFINITY;
   if (pl_pair(g, m, k, p0) && k < p1) {
@@ -449,8 +449,8 @@ __global__ void k_mean_shift(GridX g, float* __restrict__ r, const double* __res
   int i, j; long m; int pz;
   wl_tile(g, m, pz);
   // Julia: sum(p.r) is Float32 (pairwise); s = that / length(inside).  We round the double sum to Float32 first.
-  const float s = (float)(*sum) / (float)n_inside;
-  if (fabsf(s) <= 2.f * 1.1920929e-7f) return;
+  const float s = wl_shift_mean(*sum, n_inside);
+  if (!wl_shift_due(*sum, n_inside)) return;
   if (!cell_ij(g, m, i, j) || !interior_ij(g, i, j)) return;
   const long o = m + (long)(g.k0 + pz) * g.sz;
   r[o] = r[o] - s;
@@ -590,7 +590,7 @@ __global__ void k_jacobi_march_cl(GridX g, float* __restrict__ rout, const float
   int i, j; long m; int pz;
   wl_tile(g, m, pz);
   float c = 0.f;
-  if (SHIFT) { const float sm = (float)(*sum) / (float)n_inside; c = (fabsf(sm) <= 2.f * 1.1920929e-7f) ? 0.f : sm; }
+  if (SHIFT) c = wl_shift_due(*sum, n_inside) ? wl_shift_mean(*sum, n_inside) : 0.f;
   float acc = 0.f, mx = 0.f;      // a thread's |r| over its ≤ zchunk planes in Float32, across threads in Float64
   const int ks = g.k0 + pz * zchunk, ke = (ks + zchunk < g.k1) ? ks + zchunk : g.k1;
   const bool live = cell_ij(g, m, i, j) && interior_ij(g, i, j) && ks < ke;
@@ -660,8 +660,8 @@ __global__ void k_jacobi_pp(GridX g, float* __restrict__ rout, const float* __re
 __global__ void k_shift_norms(GridX g, float* __restrict__ r, const double* __restrict__ sum, double n_inside, double* __restrict__ part, float* __restrict__ pmax) {
   int i, j; long m; int pz;
   wl_tile(g, m, pz);
-  const float s = (float)(*sum) / (float)n_inside;
-  const bool shift = !(fabsf(s) <= 2.f * 1.1920929e-7f);
+  const float s = wl_shift_mean(*sum, n_inside);
+  const bool shift = wl_shift_due(*sum, n_inside);
   double acc = 0.0; float mx = 0.f;
   const int nsl = wl_nslots(g);
   if (cell_ij(g, m, i, j) && interior_ij(g, i, j)) {
@@ -1155,13 +1155,14 @@ int project_unscale_split(float* u, const float* L, const float* x, float* pout,
   WL_LAUNCH_CHECK(); return 0;
 }
 // solver!'s break test on the device (src/MultiLevelPoisson.jl:122 with l1n_tol, src/Poisson.jl:194): res_f[out_slot] = 1 if L₁ < r1tol ∧ L∞ < rinftol — the statements
-// wl_mg::solve evaluates on the host from the same two numbers — and, with check_head, the fused head's mean-shift test |Σr/N| ≤ 2eps (src/Poisson.jl:96) as well.
-// The host takes its decision from this flag (read back with the norms), so a tail kernel gated by it and the solver loop can never disagree.
+// wl_mg::solve evaluates on the host from the same two numbers — else 0.  check_head = 1: first, the fused head's mean-shift test on Σr (res_d[0], wl_shift_due):
+// −1 if the shift is due (the speculative solve is discarded whatever the norms say); check_head = 2 (test hook): −1 whatever Σr is.
+// The host takes every one of these decisions from this flag (read back with the norms), so a tail kernel gated by it (runs iff > 0) and the host never disagree.
 __global__ void k_decide(const double* __restrict__ res_d, float* __restrict__ res_f, double r1tol, double rinftol, double ninside, int check_head, int slot_d, int slot_f, int out_slot) {
   const float rnew = (float)res_d[slot_d], rinf = res_f[slot_f];
-  bool ok = (double)rnew < r1tol && (double)rinf < rinftol;
-  if (check_head) { const float sm = (float)res_d[0] / (float)ninside; ok = ok && fabsf(sm) <= 2.f * 1.1920929e-7f; }
-  res_f[out_slot] = ok ? 1.f : 0.f;
+  const bool ok = (double)rnew < r1tol && (double)rinf < rinftol;
+  const bool head_due = check_head == 2 || (check_head == 1 && wl_shift_due(res_d[0], ninside));
+  res_f[out_slot] = head_due ? -1.f : (ok ? 1.f : 0.f);
 }
 int decide_converged(const RedWs& ws, double r1tol, double rinftol, double ninside, int check_head, int slot_d, int slot_f, int out_slot, hipStream_t s) {
   hipLaunchKernelGGL(k_decide, dim3(1), dim3(1), 0, s, (const double*)ws.res_d, ws.res_f, r1tol, rinftol, ninside, check_head, slot_d, slot_f, out_slot);

@@ -483,7 +483,7 @@ struct wl_sim {
   int itmx = 32;             // solver!'s iteration cap (src/MultiLevelPoisson.jl:108); the multi-GPU rehearsal (tools/slab_rank_bench.py) lowers it to the 1 V-cycle the real run takes
   bool use_resjac = true;    // projection head + first Jacobi! in one launch (wl_resjac.hip) where eligible
   bool use_headspec = true;  // … and the first V-cycle queued behind it without waiting for Σr (single GPU)
-  bool resjac_force_redo = false;   // test hook: behave as if the mean shift were always due (exercises the redo path)
+  bool resjac_force_redo = false;   // test hook: behave as if the mean shift were always due (exercises the redo path; with the tail armed, k_decide declares it)
   bool redo_unannounced = false;    // test hook: … and do not let the BC! deferral know in advance (as with a real shift)
   long n_tailfuse = 0;       // projections whose velocity update ran inside the corrector's conv_diff!
   long n_resjac = 0, n_resjac_redo = 0;   // how often the fused head stood / had to be redone because the mean shift was due
@@ -494,7 +494,7 @@ struct wl_sim {
   bool cfl_done = false;
   static constexpr int CFL_SLOT = 5;   // res_f slot of CFL's maximum (not slot 0: a tail queued ahead of the solver's read must leave the head's L∞ there for the log)
   bool use_tailspec = true;  // the projection tail is queued behind the smoother before the host has read the norms, gated on the device by the break test (single GPU)
-  long n_tailspec = 0;
+  long n_tailspec = 0, n_tailspec_armed = 0;   // projection tails that ran gated / solves the gated tail was armed for (the difference: withheld — capped, or the head redone)
   int project(float w, hipStream_t s, bool with_cfl = false, bool defer_tail = false) {    // mom_project! :223-232 (defer_tail: inside mom_step!, the corrector follows)
     const float dtl = w * dt.back();
     cfl_done = false;
@@ -550,11 +550,13 @@ struct wl_sim {
           std::swap(p, ps); l0.x = p;
           std::swap(l0.r, l0.eps);
           mg->jacobi0_done = true;
-          if (use_tailspec && tail_gateable && !resjac_force_redo) { mg->spec_tail = launch_tail; mg->spec_check_head = true; }
+          // armed: the device decides whether the head stands (k_decide: −1 = shift due; the resjac=2/3 hook declares it due there too), the host reads that flag
+          struct SpecClear { wl_mg* m; ~SpecClear() { m->spec_tail = nullptr; m->spec_check_head = 0; } } spec_clear{mg};   // the hook captures this frame: never outlives it
+          if (use_tailspec && tail_gateable) { mg->spec_tail = launch_tail; mg->spec_check_head = resjac_force_redo ? 2 : 1; n_tailspec_armed++; }
           WL_TRY(mg->solve(2e-3, itmx, nullptr, nullptr, nullptr, s, true, nullptr, nullptr));
           tail_stood = mg->tail_stood; if (tail_stood) n_tailspec++;
-          const float sm = (float)mg->first_hd0 / (float)(double)wl_ninside_global(mg->lv[0].g);
-          if (std::fabs(sm) <= 2.f * 1.1920929e-7f && !resjac_force_redo) { head_done = true; solved = true; n_resjac++; resjac_redo_run = 0; }
+          const bool due = mg->head_decided ? mg->head_due : (resjac_force_redo || wl_shift_due(mg->first_hd0, (double)wl_ninside_global(mg->lv[0].g)));
+          if (!due) { head_done = true; solved = true; n_resjac++; resjac_redo_run = 0; }
           else {
             std::swap(l0.r, l0.eps); std::swap(p, ps); l0.x = p;
             mg->n.pop_back(); mg->jacobi0_done = false;
@@ -565,8 +567,7 @@ struct wl_sim {
         WL_TRY(wl::combine_results(comm, mg->ws, s));            // z-slabs: Σr, L₁ (sums) and L∞ (max) over the ranks — every rank takes the same branch below
         double hd2[2]; WL_TRY(wl::read_results(mg->ws, hd2, 2, &pre_rinf, 1, s));
         const double sr = hd2[0]; pre_r1 = hd2[1];
-        const float sm = (float)sr / (float)(double)wl_ninside_global(mg->lv[0].g);
-        if (std::fabs(sm) <= 2.f * 1.1920929e-7f && !resjac_force_redo) {                                       // src/Poisson.jl:96: no shift — the fused results stand
+        if (!wl_shift_due(sr, (double)wl_ninside_global(mg->lv[0].g)) && !resjac_force_redo) {                                       // src/Poisson.jl:96: no shift — the fused results stand
           std::swap(p, ps); l0.x = p;
           std::swap(l0.r, l0.eps);
           mg->jacobi0_done = true; head_done = true; n_resjac++; resjac_redo_run = 0;
@@ -632,7 +633,12 @@ struct wl_sim {
     dt.push_back(std::fmin(10.f, 1.0f / (mx + 5 * d.nu)));
     return 0;
   }
-  int mom_step(hipStream_t s, bool more_follow = false) {                                // mom_step! :156-167 (more_follow: wl_sim_mom_steps — another step comes inside the same call)
+  int mom_step(hipStream_t s, bool more_follow = false) {
+    const int rc = mom_step_body(s, more_follow);
+    if (rc != 0) { bc_deferred = false; dt_pending = false; }   // a failed step leaves no deferred BC! and no Δt on the device for the next call to take
+    return rc;
+  }
+  int mom_step_body(hipStream_t s, bool more_follow) {                                   // mom_step! :156-167 (more_follow: wl_sim_mom_steps — another step comes inside the same call)
     ProfScope pstep(WL_PROF_STEP, s);
     // u⁰ .= u ; scale_u!(a,0): when the handle owns both arrays the copy is a pointer swap — the predictor overwrites
     // every interior cell of u (BDIM! with pre=0) and BC! every ghost cell, so nothing of the old u survives anyway.
@@ -917,6 +923,7 @@ int wl_sim_counter(wl_sim* s, const char* name, long* out) {
   if (n == "tailfuse") { *out = s->n_tailfuse; return 0; }
   if (n == "bcdefer") { *out = s->n_bcdefer; return 0; }
   if (n == "tailspec") { *out = s->n_tailspec; return 0; }
+  if (n == "tailspec_armed") { *out = s->n_tailspec_armed; return 0; }
   if (n == "xdefer") { *out = s->mg->last_xdefer; return 0; }
   wl_set_error("unknown counter " + n); return WL_EINVAL;
 }

@@ -206,6 +206,10 @@ class MultiLevelPoisson:
         k = lib().wl_mg_last_log(self._h, a, b, c, cap)
         return np.array(a[:k]), np.array(b[:k]), np.array(c[:k])
 
+    def shift_path(self):
+        """how the last solve applied residual!'s mean shift: 0 its own pass, 1 inside the finest level's z-marching Jacobi!, 2 the fused projection head"""
+        return int(lib().wl_mg_shift_path(self._h))
+
     def level_norms(self, l=0):
         lv = self.levels[l]
         l1, linf = C.c_double(), C.c_float()
