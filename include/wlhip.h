@@ -269,6 +269,33 @@ int wl_sim_viscous_force_body(wl_sim* s, const wl_body* host_body, double out[3]
 int wl_sim_pressure_force_sphere(wl_sim* s, const float* host_center, float R, double* host_out, void* stream);
 int wl_sim_viscous_force_sphere(wl_sim* s, const float* center, float R, double* out, void* stream);   /* viscous_force(sim) src/Metrics.jl:140-154 (single domain) */
 
+/* ---- composite bodies: closed-form leaves under rigid maps, combined by set operations (src/Body.jl:91-107, RigidMap.jl) -------
+ * A wl_bodyset is a postfix program of at most WL_BODYSET_MAX nodes (evaluation stack at most WL_BODYSET_STACK deep, final depth 1).
+ * Leaf kinds are those of wl_body plus WL_BODY_CAPSULE: sdf = |ξ−p|−R, p the point of the segment c ± h·m (m the body-frame axis,
+ * normalised by the library, h ≥ 0) closest to ξ — the flat plate of WaterLily cases.  A leaf with mapped=1 is evaluated at the
+ * body-frame point ξ = R̂(x−x₀−xₚ)+xₚ of its rigid map; n = R̂ᵀg/|R̂ᵀg|, d = sdf/|R̂ᵀg|, velocity V + ω×(x−x₀−xₚ) (2-D: ω = w[0],
+ * ω×b = ω(−b₂,b₁)) (src/AutoBody.jl:29-37).  An unmapped leaf measures exactly as wl_body does, with V = 0.
+ * UNION takes the smaller (d,n,V) tuple in Julia's isless order (min), INTERSECT the larger (max), NEGATE gives (−d,−n,V); a − b is
+ * a ∩ (−b).  σ holds the raw sdf of a single-leaf program and measure(body,x;fastd²=(2+ϵ)²)[1] otherwise (src/Body.jl:67,74).
+ * Malformed programs return WL_EINVAL before anything is launched. */
+enum { WL_BODY_CAPSULE = 3 };
+enum { WL_OP_LEAF = 0, WL_OP_UNION = 1, WL_OP_INTERSECT = 2, WL_OP_NEGATE = 3 };
+#define WL_BODYSET_MAX 16
+#define WL_BODYSET_STACK 8
+typedef struct wl_rigid_map { float x0[3]; float xp[3]; float R[9]; float V[3]; float w[3]; } wl_rigid_map;   /* R row-major (2-D: upper-left 2x2) */
+typedef struct wl_body_node { int32_t op; int32_t kind; float c[3]; float R; float m[3]; float h; int32_t mapped; wl_rigid_map map; } wl_body_node;
+typedef struct wl_bodyset { int32_t n; wl_body_node node[WL_BODYSET_MAX]; } wl_bodyset;
+/* measure(body,x;fastd²) at npts host points host_x[npts·D] (point-major); writes host_d[npts], host_n[npts·D], host_V[npts·D]; synchronises */
+int wl_bodyset_measure_points(const wl_bodyset* host_set, int D, const float* host_x, int npts, float fastd2, float* host_d, float* host_n, float* host_V, void* stream);
+/* measure!(flow,body;ϵ) on the caller's arrays: one pass writes every element of σ (interior), μ₀, μ₁, V, then BC!(μ₀), BC!(V) */
+int wl_measure_bodyset(float* sigma, float* mu0, float* mu1, float* V, const wl_grid* g, const wl_bodyset* host_set, float eps, int exitBC, uint32_t perdir_mask, void* stream);
+/* pressure / viscous force (src/Metrics.jl:116-154); host_x0 non-NULL: the moment about x₀ instead (:169-188, 2-D: out[0] = out[1]) */
+int wl_pressure_force_bodyset(const float* host_x0, const float* p, const wl_grid* g, const wl_bodyset* host_set, double out[3], void* stream);
+int wl_viscous_force_bodyset(const float* host_x0, const float* u, const wl_grid* g, float nu, const wl_bodyset* host_set, double out[3], void* stream);
+int wl_sim_measure_bodyset(wl_sim* s, const wl_bodyset* host_set, float eps, void* stream);       /* measure! + halos + update!(pois), as wl_sim_measure_body */
+int wl_sim_pressure_force_bodyset(wl_sim* s, const float* host_x0, const wl_bodyset* host_set, double out[3], void* stream);   /* collective on z-slabs */
+int wl_sim_viscous_force_bodyset(wl_sim* s, const float* host_x0, const wl_bodyset* host_set, double out[3], void* stream);
+
 /* ---- multi-GPU: z-slab decomposition, one process per GPU (NEW — the reference has no multi-device path,
  * /root/reference/README.md:153-155).  A wl_comm carries the two primitives the slab path needs, stream-ordered:
  * a nearest-neighbour plane exchange along z and an all-gather; scalars (Σr, L₁, L∞, max σ) are combined on

@@ -11,3 +11,5 @@ from .poisson import (pcg_, poisson_solver_, GaussSeidelRB_, Jacobi_, L1, Linf, 
 from .metrics import MeanFlow, load_checkpoint, save_checkpoint  # noqa: F401
 from .simulation import (FusedSimulation, Simulation, measure_, pressure_force, pressure_moment, viscous_force,  # noqa: F401
                          viscous_moment)
+from . import bodies  # noqa: F401,E402
+from .bodies import Body, RigidMap, SetBody, setmap  # noqa: F401,E402

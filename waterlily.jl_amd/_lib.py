@@ -37,6 +37,25 @@ def make_body(body, D):
     return b
 
 
+class wl_rigid_map(C.Structure):
+    """include/wlhip.h wl_rigid_map: RigidMap's x₀, xₚ, R̂ (row-major 3x3), V, ω"""
+    _fields_ = [("x0", C.c_float * 3), ("xp", C.c_float * 3), ("R", C.c_float * 9), ("V", C.c_float * 3), ("w", C.c_float * 3)]
+
+
+class wl_body_node(C.Structure):
+    """include/wlhip.h wl_body_node: one node of a postfix body program"""
+    _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("c", C.c_float * 3), ("R", C.c_float), ("m", C.c_float * 3), ("h", C.c_float),
+                ("mapped", C.c_int32), ("map", wl_rigid_map)]
+
+
+WL_BODYSET_MAX, WL_BODYSET_STACK = 16, 8
+
+
+class wl_bodyset(C.Structure):
+    """include/wlhip.h wl_bodyset"""
+    _fields_ = [("n", C.c_int32), ("node", wl_body_node * WL_BODYSET_MAX)]
+
+
 class wl_sim_desc(C.Structure):
     _fields_ = [("D", C.c_int32), ("dims", C.c_int32 * 3), ("uBC", C.c_float * 3), ("nu", C.c_float), ("dt0", C.c_float),
                 ("perdir_mask", C.c_uint32), ("exitBC", C.c_int32), ("scheme", C.c_int32), ("has_body", C.c_int32),
@@ -166,7 +185,13 @@ SIGNATURES = {
     "wl_sim_measure_body": (i32, [P, C.POINTER(wl_body), f32, P]),
     "wl_sim_pressure_force_body": (i32, [P, C.POINTER(wl_body), C.POINTER(f64), P]),
     "wl_sim_viscous_force_body": (i32, [P, C.POINTER(wl_body), C.POINTER(f64), P]),
-
+    "wl_bodyset_measure_points": (i32, [C.POINTER(wl_bodyset), i32, C.POINTER(f32), i32, f32, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), P]),
+    "wl_measure_bodyset": (i32, [P, P, P, P, G, C.POINTER(wl_bodyset), f32, i32, C.c_uint32, P]),
+    "wl_pressure_force_bodyset": (i32, [C.POINTER(f32), P, G, C.POINTER(wl_bodyset), C.POINTER(f64), P]),
+    "wl_viscous_force_bodyset": (i32, [C.POINTER(f32), P, G, f32, C.POINTER(wl_bodyset), C.POINTER(f64), P]),
+    "wl_sim_measure_bodyset": (i32, [P, C.POINTER(wl_bodyset), f32, P]),
+    "wl_sim_pressure_force_bodyset": (i32, [P, C.POINTER(f32), C.POINTER(wl_bodyset), C.POINTER(f64), P]),
+    "wl_sim_viscous_force_bodyset": (i32, [P, C.POINTER(f32), C.POINTER(wl_bodyset), C.POINTER(f64), P]),
     "wl_sim_viscous_force_sphere": (i32, [P, C.POINTER(f32), f32, C.POINTER(f64), P]),
 }
 

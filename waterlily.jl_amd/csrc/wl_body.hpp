@@ -1,0 +1,64 @@
+// Closed-form body helpers shared by the measure!/force kernels of wl_sim.hip and wl_bodyset.hip (device code, gfx950).
+#pragma once
+#include "wl_common.hpp"
+
+namespace {
+// BDIM kernel moments   src/Body.jl:54-60
+__device__ __forceinline__ float kern_(float d) { return (1 + cosf(3.14159265358979323846f * d)) / 2; }
+__device__ __forceinline__ float kern0_(float d) { return (1 + d + sinf(3.14159265358979323846f * d) / 3.14159265358979323846f) / 2; }
+__device__ __forceinline__ float kern1_(float d) { return (1 - d * d) / 4 - (d * sinf(3.14159265358979323846f * d) + (1 + cosf(3.14159265358979323846f * d)) / 3.14159265358979323846f) / (2 * 3.14159265358979323846f); }
+__device__ __forceinline__ float eps_at(float d) { d = fabsf(d); return d == 0.f ? 1.4e-45f : nextafterf(d, INFINITY) - d; }
+__device__ __forceinline__ float mu0_(float d, float e) { return d / e < -1 + sqrtf(eps_at(d)) ? 0.f : kern0_(fminf(d / e, 1.f)); }
+__device__ __forceinline__ float mu1_(float d, float e) { return e * kern1_(fminf(fmaxf(d / e, -1.f), 1.f)); }
+// Closed-form AutoBody (src/AutoBody.jl:21,29-37): kind 1 sdf = |m∘(x−c)|−R (sphere/circle; an axis with m=0 is dropped: cylinder
+// along it), kind 2 sdf = m·(x−c) (plane, m need not be unit).  The map x−V·t is folded into c by the caller, V is the body velocity.
+struct BodyArg { int kind; float c[3], R, m[3], V[3]; };
+template <int D>
+__device__ __forceinline__ float body_sdf(const BodyArg& b, const float* x) {
+  float s = 0.f;
+  if (b.kind == 2) { for (int q = 0; q < D; q++) s += b.m[q] * (x[q] - b.c[q]); return s; }
+  for (int q = 0; q < D; q++) { const float dx = b.m[q] * (x[q] - b.c[q]); s += dx * dx; }
+  return sqrtf(s) - b.R;
+}
+// measure(body,x;fastd²): returns true when n was evaluated (then V = the body velocity), false on the early exits (n = V = 0)
+template <int D>
+__device__ __forceinline__ bool body_measure(const BodyArg& b, const float* x, float fastd2, float& d, float* n) {
+  float rr = 0.f;
+  for (int q = 0; q < D; q++) n[q] = 0.f;
+  if (b.kind == 2) d = body_sdf<D>(b, x);
+  else { float s = 0.f; for (int q = 0; q < D; q++) { const float dx = b.m[q] * (x[q] - b.c[q]); s += dx * dx; } rr = sqrtf(s); d = rr - b.R; }
+  if (d * d > fastd2) return false;
+  float gq[3]; bool nan = false;
+  for (int q = 0; q < D; q++) { gq[q] = b.kind == 2 ? b.m[q] : (b.m[q] * (x[q] - b.c[q])) / rr; nan = nan || isnan(gq[q]); }
+  if (nan) return false;
+  float mm = 0.f; for (int q = 0; q < D; q++) mm += gq[q] * gq[q];
+  mm = sqrtf(mm); d /= mm;
+  for (int q = 0; q < D; q++) n[q] = gq[q] / mm;
+  return true;
+}
+// cross(a,b) as the reference's broadcast stores it: the 3-D vector product, in 2-D the scalar a₁b₂−a₂b₁ in every component
+template <int D>
+__device__ __forceinline__ void cross_(const float* a, const float* b, float* o) {
+  if (D == 2) { const float m = a[0] * b[1] - a[1] * b[0]; o[0] = m; o[1] = m; o[2] = 0.f; }
+  else { o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0]; }
+}
+struct MomArg { int on; float x0[3]; };      // on: moments about x0 (pressure_moment / viscous_moment, src/Metrics.jl:169-188) instead of forces
+}  // namespace
+
+// A validated wl_bodyset as the kernels take it (by value, kernarg memory): components beyond D zeroed, capsule axes normalised; depth = the deepest the stack gets
+struct SetArg { int32_t n; int32_t leaf_root; int32_t depth; wl_body_node node[WL_BODYSET_MAX]; };
+namespace {
+__device__ __forceinline__ BodyArg body_arg(const wl_body_node& b) {
+  BodyArg a; a.kind = b.kind; a.R = b.R;
+  for (int q = 0; q < 3; q++) { a.c[q] = b.c[q]; a.m[q] = b.m[q]; a.V[q] = 0.f; }
+  return a;
+}
+}  // namespace
+struct wl_comm;
+namespace wl {
+int bodyset_prepare(int D, const wl_bodyset* s, SetArg* out);      // WL_EINVAL (and the reason) for a malformed program
+int bodyset_measure_fields(float* sigma, float* mu0, float* mu1, float* V, const GridX& G, const SetArg& P, float eps, int exitBC, unsigned perdir, hipStream_t q);
+int bodyset_force_partials(int which, const float* a, float nu, const GridX& G, const SetArg& P, const float* x0, dim3 grid, double* part, hipStream_t q);
+// force/moment read-out (wl_sim.hip): `partials` writes 3·grid.x Float64 partial sums, then the fixed-order finish, the sum over ranks and the read-back
+int force_reduce_with(const GridX& G, const RedWs& ws, wl_comm* comm, double* out, hipStream_t q, const std::function<int(dim3, double*, hipStream_t)>& partials);
+}  // namespace wl

@@ -9,6 +9,7 @@
 #include "wl_common.hpp"
 #include <algorithm>
 #include "wl_mg.hpp"
+#include "wl_body.hpp"
 
 namespace {
 __device__ __forceinline__ bool cell_ij(const GridX& g, long m, int& i, int& j) {
@@ -49,39 +50,6 @@ __global__ void k_apply_const(GridX g, float* __restrict__ u, float U0, float U1
   u[o] = U0; u[g.cs + o] = U1; if (D == 3) u[2 * g.cs + o] = U2;
 }
 
-// BDIM kernel moments   src/Body.jl:54-60
-__device__ __forceinline__ float kern_(float d) { return (1 + cosf(3.14159265358979323846f * d)) / 2; }
-__device__ __forceinline__ float kern0_(float d) { return (1 + d + sinf(3.14159265358979323846f * d) / 3.14159265358979323846f) / 2; }
-__device__ __forceinline__ float kern1_(float d) { return (1 - d * d) / 4 - (d * sinf(3.14159265358979323846f * d) + (1 + cosf(3.14159265358979323846f * d)) / 3.14159265358979323846f) / (2 * 3.14159265358979323846f); }
-__device__ __forceinline__ float eps_at(float d) { d = fabsf(d); return d == 0.f ? 1.4e-45f : nextafterf(d, INFINITY) - d; }
-__device__ __forceinline__ float mu0_(float d, float e) { return d / e < -1 + sqrtf(eps_at(d)) ? 0.f : kern0_(fminf(d / e, 1.f)); }
-__device__ __forceinline__ float mu1_(float d, float e) { return e * kern1_(fminf(fmaxf(d / e, -1.f), 1.f)); }
-// Closed-form AutoBody (src/AutoBody.jl:21,29-37): kind 1 sdf = |m∘(x−c)|−R (sphere/circle; an axis with m=0 is dropped: cylinder
-// along it), kind 2 sdf = m·(x−c) (plane, m need not be unit).  The map x−V·t is folded into c by the caller, V is the body velocity.
-struct BodyArg { int kind; float c[3], R, m[3], V[3]; };
-template <int D>
-__device__ __forceinline__ float body_sdf(const BodyArg& b, const float* x) {
-  float s = 0.f;
-  if (b.kind == 2) { for (int q = 0; q < D; q++) s += b.m[q] * (x[q] - b.c[q]); return s; }
-  for (int q = 0; q < D; q++) { const float dx = b.m[q] * (x[q] - b.c[q]); s += dx * dx; }
-  return sqrtf(s) - b.R;
-}
-// measure(body,x;fastd²): returns true when n was evaluated (then V = the body velocity), false on the early exits (n = V = 0)
-template <int D>
-__device__ __forceinline__ bool body_measure(const BodyArg& b, const float* x, float fastd2, float& d, float* n) {
-  float rr = 0.f;
-  for (int q = 0; q < D; q++) n[q] = 0.f;
-  if (b.kind == 2) d = body_sdf<D>(b, x);
-  else { float s = 0.f; for (int q = 0; q < D; q++) { const float dx = b.m[q] * (x[q] - b.c[q]); s += dx * dx; } rr = sqrtf(s); d = rr - b.R; }
-  if (d * d > fastd2) return false;
-  float gq[3]; bool nan = false;
-  for (int q = 0; q < D; q++) { gq[q] = b.kind == 2 ? b.m[q] : (b.m[q] * (x[q] - b.c[q])) / rr; nan = nan || isnan(gq[q]); }
-  if (nan) return false;
-  float mm = 0.f; for (int q = 0; q < D; q++) mm += gq[q] * gq[q];
-  mm = sqrtf(mm); d /= mm;
-  for (int q = 0; q < D; q++) n[q] = gq[q] / mm;
-  return true;
-}
 // measure!(flow,body;ϵ) for the sphere: fills σ(sdf), μ₀, μ₁, V(=0) on the interior   src/Body.jl:28-48
 template <int D>
 __global__ void k_measure_body(GridX g, float* __restrict__ sig, float* __restrict__ mu0, float* __restrict__ mu1, float* __restrict__ V, BodyArg bd, float e) {
@@ -108,13 +76,6 @@ __global__ void k_measure_body(GridX g, float* __restrict__ sig, float* __restri
     for (int a = 0; a < D; a++) mu0[(long)a * g.cs + o] = 0.f;
   }
 }
-// cross(a,b) as the reference's broadcast stores it: the 3-D vector product, in 2-D the scalar a₁b₂−a₂b₁ in every component
-template <int D>
-__device__ __forceinline__ void cross_(const float* a, const float* b, float* o) {
-  if (D == 2) { const float m = a[0] * b[1] - a[1] * b[0]; o[0] = m; o[1] = m; o[2] = 0.f; }
-  else { o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0]; }
-}
-struct MomArg { int on; float x0[3]; };      // on: moments about x0 (pressure_moment / viscous_moment, src/Metrics.jl:169-188) instead of forces
 // pressure_force: Σ_inside p[I]·n·kern(clamp(d,-1,1)) in Float64   src/Metrics.jl:116-133
 template <int D>
 __global__ void k_pforce_body(GridX g, const float* __restrict__ p, BodyArg bd, MomArg mo, double* __restrict__ part) {
@@ -996,13 +957,13 @@ static int measure_fields(float* sigma, float* mu0, float* mu1, float* V, const 
 }
 // which: 0 pressure_force(p) (src/Metrics.jl:116-133), 1 viscous_force(u,ν) (:140-154); Float64 partial sums, flow.f untouched.
 // On z-slabs every rank sums its own planes and the per-rank sums are added on device (one 128-byte all-gather).
-static int force_reduce(int which, const float* a, float nu, const GridX& G, const BodyArg& bd, const RedWs& ws, wl_comm* comm, double* out, hipStream_t q, const float* x0 = nullptr) {
+}  // extern "C"
+namespace wl {
+int force_reduce_with(const GridX& G, const RedWs& ws, wl_comm* comm, double* out, hipStream_t q, const std::function<int(dim3, double*, hipStream_t)>& partials) {
   const int D = G.D;
-  MomArg mo{}; if (x0) { mo.on = 1; for (int c = 0; c < D; c++) mo.x0[c] = x0[c]; }
   dim3 grid = wl_plane_grid(G, wl_red_slots(G, G.k1 - G.k0));
   // partials need 3*grid.x doubles (<= 3*WL_REDPART): pa and pb are contiguous (2*WL_MAXPART doubles)
-  if (which == 0) { DSEL(D, k_pforce_body, grid, dim3(WL_BLOCK), 0, q, G, a, bd, mo, ws.pa); }
-  else { DSEL(D, k_vforce_body, grid, dim3(WL_BLOCK), 0, q, G, a, nu, bd, mo, ws.pa); }
+  WL_TRY(partials(grid, ws.pa, q));
   hipLaunchKernelGGL(k_fin3, dim3(1), dim3(WL_BLOCK), 0, q, ws.pa, (int)grid.x, ws.res_d + 4);
   WL_LAUNCH_CHECK();
   WL_TRY(wl::combine_results(comm, ws, q));
@@ -1012,6 +973,17 @@ static int force_reduce(int which, const float* a, float nu, const GridX& G, con
   WL_HIP(hipStreamSynchronize(q));
   for (int c = 0; c < D; c++) out[c] = cx.h_d[c];
   return 0;
+}
+}  // namespace wl
+extern "C" {
+static int force_reduce(int which, const float* a, float nu, const GridX& G, const BodyArg& bd, const RedWs& ws, wl_comm* comm, double* out, hipStream_t q, const float* x0 = nullptr) {
+  const int D = G.D;
+  MomArg mo{}; if (x0) { mo.on = 1; for (int c = 0; c < D; c++) mo.x0[c] = x0[c]; }
+  return wl::force_reduce_with(G, ws, comm, out, q, [&](dim3 grid, double* part, hipStream_t s) -> int {
+    if (which == 0) { DSEL(D, k_pforce_body, grid, dim3(WL_BLOCK), 0, s, G, a, bd, mo, part); }
+    else { DSEL(D, k_vforce_body, grid, dim3(WL_BLOCK), 0, s, G, a, nu, bd, mo, part); }
+    return 0;
+  });
 }
 int wl_measure_body(float* sigma, float* mu0, float* mu1, float* V, const wl_grid* g, const wl_body* body, float eps, int exitBC, uint32_t perdir_mask, void* st) {
   WL_CHECK(wl_grid_ok(g), "bad wl_grid"); WL_CHECK(sigma && mu0 && mu1 && V, "null field");
@@ -1067,6 +1039,26 @@ int wl_sim_viscous_force_body(wl_sim* s, const wl_body* body, double* out, void*
   WL_TRY(s->sync_u(wl_stream(st)));                  // ∂u/∂z at the slab faces reads the neighbours' planes
   return force_reduce(1, s->u, s->d.nu, s->G, bd, s->mg->ws, s->comm, out, wl_stream(st));
 }
+int wl_sim_measure_bodyset(wl_sim* s, const wl_bodyset* set, float eps, void* st) {
+  WL_CHECK(s, "null wl_sim"); WL_CHECK(s->d.has_body && s->mu1 && s->V, "simulation was created with has_body=0");
+  SetArg P; WL_TRY(wl::bodyset_prepare(s->d.D, set, &P));
+  hipStream_t q = wl_stream(st); const GridX& G = s->G; const int D = s->d.D;
+  WL_TRY(wl::bodyset_measure_fields(s->sigma, s->mu0, s->mu1, s->V, G, P, eps, s->d.exitBC, s->d.perdir_mask, q));
+  WL_TRY(wl::halo(s->comm, s->mu0, G, D, 2, q)); WL_TRY(wl::halo(s->comm, s->V, G, D, 2, q));
+  WL_TRY(s->refresh_body_mask(q));
+  return s->mg->update(q);                                                                                                          // WaterLily.jl:148
+}
+static int sim_force_bodyset(int which, wl_sim* s, const float* x0, const wl_bodyset* set, double* out, void* st) {
+  WL_CHECK(s && out, "null wl_sim / out");
+  SetArg P; WL_TRY(wl::bodyset_prepare(s->d.D, set, &P));
+  hipStream_t q = wl_stream(st);
+  if (which == 1) WL_TRY(s->sync_u(q));              // ∂u/∂z at the slab faces reads the neighbours' planes
+  const float* a = which == 0 ? s->p : s->u; const float nu = which == 0 ? 0.f : s->d.nu; const GridX& G = s->G;
+  return wl::force_reduce_with(G, s->mg->ws, s->comm, out, q,
+                               [&](dim3 grid, double* part, hipStream_t qq) { return wl::bodyset_force_partials(which, a, nu, G, P, x0, grid, part, qq); });
+}
+int wl_sim_pressure_force_bodyset(wl_sim* s, const float* x0, const wl_bodyset* set, double* out, void* st) { return sim_force_bodyset(0, s, x0, set, out, st); }
+int wl_sim_viscous_force_bodyset(wl_sim* s, const float* x0, const wl_bodyset* set, double* out, void* st) { return sim_force_bodyset(1, s, x0, set, out, st); }
 int wl_sim_measure_sphere(wl_sim* s, const float* c, float R, float eps, void* st) { const wl_body b = sphere_body(c, R); return wl_sim_measure_body(s, &b, eps, st); }
 int wl_sim_pressure_force_sphere(wl_sim* s, const float* c, float R, double* out, void* st) { const wl_body b = sphere_body(c, R); return wl_sim_pressure_force_body(s, &b, out, st); }
 int wl_sim_viscous_force_sphere(wl_sim* s, const float* c, float R, double* out, void* st) { const wl_body b = sphere_body(c, R); return wl_sim_viscous_force_body(s, &b, out, st); }

@@ -23,7 +23,7 @@ using LinearAlgebra
 import WaterLily: BC!, perBC!, exitBC!, apply!, conv_diff!, accelerate!, BDIM!, scale_u!, CFL, L₂, mom_step!, mom_project!, measure!,
                   set_diag!, update!, mult!, residual!, increment!, Jacobi!, GaussSeidelRB!, pcg!, restrict!, prolongate!,
                   restrictL!, solver!, L₁, L∞, quick, vanLeer, cds, loc, Flow, Poisson, MultiLevelPoisson, AbstractPoisson,
-                  AbstractFlow, AbstractBody, NoBody
+                  AbstractFlow, AbstractBody, NoBody, SetBody, RigidMap
 
 const libwlhip = get(ENV, "WLHIP_LIB", "libwlhip.so")
 
@@ -433,5 +433,92 @@ end
 WaterLily.pressure_force(p::HA, df::HA, body::AbstractBody, t=0) = WaterLily.pressure_force(Array(p), Array(df), body, t)
 WaterLily.viscous_force(u::HA, ν, df::HA, body::AbstractBody, t=0) = WaterLily.viscous_force(Array(u), ν, Array(df), body, t)
 
-export HipArray, HipMultiLevel, HipBody
+# composite bodies on the device (include/wlhip.h wl_bodyset): HipBody leaves, optionally under the reference's RigidMap, combined by
+# SetBody (∪ ∩ −).  The tree is flattened into a postfix program and R̂ is passed as the map stores it; measure! of a moving body is
+# then one device pass per step instead of the host shadow's O(N) work and four uploads.
+struct WlRigidMap; x0::NTuple{3,Cfloat}; xp::NTuple{3,Cfloat}; R::NTuple{9,Cfloat}; V::NTuple{3,Cfloat}; w::NTuple{3,Cfloat}; end     # wl_rigid_map
+struct WlBodyNode; op::Int32; kind::Int32; c::NTuple{3,Cfloat}; R::Cfloat; m::NTuple{3,Cfloat}; h::Cfloat; mapped::Int32; map::WlRigidMap; end   # wl_body_node
+struct WlBodySet; n::Int32; node::NTuple{16,WlBodyNode}; end                                                                      # wl_bodyset
+"""
+    HipCapsule(c, R, axis, h)
+
+sdf = |x−p|−R, p the point of the segment c ± h·axis closest to x: the flat plate of WaterLily cases (WL_BODY_CAPSULE).
+"""
+struct HipCapsule{C} <: AbstractBody
+    c::C; R::Float32; axis::NTuple{3,Cfloat}; h::Float32
+end
+HipCapsule(c, R, axis, h) = HipCapsule(c, Float32(R), pad3(axis), Float32(h))
+"""
+    HipRigidBody(shape, map::RigidMap)
+
+A closed-form leaf (HipBody or HipCapsule) evaluated at ξ = map(x).  The field is named `map`, so the reference's
+`setmap(body; θ, ω, …)` works on it (and on SetBody trees of them) unchanged.
+"""
+struct HipRigidBody{M} <: AbstractBody
+    shape::Union{HipBody,HipCapsule}
+    map::M
+end
+const DeviceSet = Union{HipRigidBody,HipCapsule,SetBody}
+device_ok(::Union{HipBody,HipRigidBody,HipCapsule}) = true
+device_ok(b::SetBody{typeof(-)}) = device_ok(b.a)
+device_ok(b::SetBody) = (b.op === min || b.op === max) && device_ok(b.a) && device_ok(b.b)
+device_ok(b) = false
+const NOMAP = WlRigidMap(pad3(()), pad3(()), ntuple(_ -> 0f0, 9), pad3(()), pad3(()))
+const IDMAP = WlRigidMap(pad3(()), pad3(()), (1f0, 0f0, 0f0, 0f0, 1f0, 0f0, 0f0, 0f0, 1f0), pad3(()), pad3(()))
+opnode(op) = WlBodyNode(Int32(op), Int32(0), pad3(()), 0f0, pad3(()), 0f0, Int32(0), NOMAP)
+leafnode(b::HipBody, D, t, mp) = WlBodyNode(Int32(0), b.kind, pad3(at(b.c, t)), b.R, ntuple(i -> i <= D ? b.m[i] : 0f0, 3), 0f0, Int32(mp !== NOMAP), mp)
+leafnode(b::HipCapsule, D, t, mp) = WlBodyNode(Int32(0), Int32(3), pad3(at(b.c, t)), b.R, b.axis, b.h, Int32(mp !== NOMAP), mp)
+wlmap(m::RigidMap, D) = WlRigidMap(pad3(m.x₀), pad3(m.xₚ), ntuple(k -> ((q, r) = divrem(k - 1, 3); q < D && r < D ? Float32(m.R̂[q+1, r+1]) : 0f0), 9),
+                                   pad3(m.V), D == 2 ? (Float32(m.ω), 0f0, 0f0) : pad3(m.ω))
+function emit!(v, b::HipBody, D, t)                 # a translating HipBody: the identity map carries its velocity
+    V = pad3(at(b.V, t))
+    push!(v, leafnode(b, D, t, all(iszero, V) ? NOMAP : WlRigidMap(pad3(()), pad3(()), IDMAP.R, V, pad3(()))))
+end
+emit!(v, b::HipCapsule, D, t) = push!(v, leafnode(b, D, t, NOMAP))
+emit!(v, b::HipRigidBody, D, t) = push!(v, leafnode(b.shape, D, t, wlmap(b.map, D)))
+emit!(v, b::SetBody{typeof(-)}, D, t) = (emit!(v, b.a, D, t); push!(v, opnode(3)))
+emit!(v, b::SetBody, D, t) = (emit!(v, b.a, D, t); emit!(v, b.b, D, t); push!(v, opnode(b.op === min ? 1 : 2)))
+function wlset(b, D, t)
+    v = WlBodyNode[]; emit!(v, b, D, t)
+    length(v) <= 16 || error("body has $(length(v)) nodes, at most 16 fit a wl_bodyset")
+    Ref(WlBodySet(Int32(length(v)), ntuple(i -> i <= length(v) ? v[i] : opnode(0), 16)))
+end
+# measure!(a::Flow,body;t,ϵ)  src/Body.jl:28-51 — anything but HipBody/HipCapsule/HipRigidBody leaves goes to the host shadow
+function measure!(a::HFlow{D}, body::DeviceSet; t=zero(Float32), ϵ=1) where {D}
+    device_ok(body) || return invoke(measure!, Tuple{HFlow{D},AbstractBody}, a, body; t, ϵ)
+    chk(ccall((:wl_measure_bodyset, libwlhip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ref{WlGrid}, Ref{WlBodySet}, Cfloat, Cint, Cuint, Ptr{Cvoid}),
+              a.σ.ptr, a.μ₀.ptr, a.μ₁.ptr, a.V.ptr, sgrid(a.σ), wlset(body, D, t), Cfloat(ϵ), Cint(a.exitBC), pmask(a.perdir), C_NULL))
+    setfield!(a.μ₁, :bodied, true)                # (μ₁, V now hold a body: has_body)
+    nothing
+end
+function WaterLily.pressure_force(p::HA, df::HA, body::DeviceSet, t=0; T=Float64)
+    device_ok(body) || return WaterLily.pressure_force(Array(p), Array(df), body, t)
+    out = zeros(Cdouble, 3); D = ndims(p)
+    chk(ccall((:wl_pressure_force_bodyset, libwlhip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Ref{WlGrid}, Ref{WlBodySet}, Ptr{Cdouble}, Ptr{Cvoid}),
+              Ptr{Cfloat}(C_NULL), p.ptr, sgrid(p), wlset(body, D, t), out, C_NULL))
+    T.(out[1:D])
+end
+function WaterLily.viscous_force(u::HA, ν, df::HA, body::DeviceSet, t=0; T=Float64)
+    device_ok(body) || return WaterLily.viscous_force(Array(u), ν, Array(df), body, t)
+    out = zeros(Cdouble, 3); D = ndims(u) - 1
+    chk(ccall((:wl_viscous_force_bodyset, libwlhip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Ref{WlGrid}, Cfloat, Ref{WlBodySet}, Ptr{Cdouble}, Ptr{Cvoid}),
+              Ptr{Cfloat}(C_NULL), u.ptr, vgrid(u), Cfloat(ν), wlset(body, D, t), out, C_NULL))
+    T.(out[1:D])
+end
+function WaterLily.pressure_moment(x₀, p::HA, df, body::DeviceSet, t=0)
+    device_ok(body) || return WaterLily.pressure_moment(x₀, Array(p), Array(df), body, t)
+    out = zeros(Cdouble, 3); D = ndims(p); x = collect(pad3(x₀))
+    chk(ccall((:wl_pressure_force_bodyset, libwlhip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Ref{WlGrid}, Ref{WlBodySet}, Ptr{Cdouble}, Ptr{Cvoid}),
+              x, p.ptr, sgrid(p), wlset(body, D, t), out, C_NULL))
+    out[1:D]
+end
+function WaterLily.viscous_moment(x₀, u::HA, ν, df, body::DeviceSet, t=0)
+    device_ok(body) || return WaterLily.viscous_moment(x₀, Array(u), ν, Array(df), body, t)
+    out = zeros(Cdouble, 3); D = ndims(u) - 1; x = collect(pad3(x₀))
+    chk(ccall((:wl_viscous_force_bodyset, libwlhip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Ref{WlGrid}, Cfloat, Ref{WlBodySet}, Ptr{Cdouble}, Ptr{Cvoid}),
+              x, u.ptr, vgrid(u), Cfloat(ν), wlset(body, D, t), out, C_NULL))
+    out[1:D]
+end
+
+export HipArray, HipMultiLevel, HipBody, HipCapsule, HipRigidBody
 end # module

@@ -11,8 +11,39 @@ from .flow import Flow, mom_step_
 from .poisson import MultiLevelPoisson
 
 
+def _is_set(body):
+    from .bodies import AbstractBody
+    return isinstance(body, AbstractBody)
+
+
+def _x0(x0, D):
+    return None if x0 is None else (C.c_float * 3)(*([float(v) for v in x0] + [0.0] * (3 - D)))
+
+
+def _bodyset_force(which, a, body, x0=None):
+    """pressure (which 0) / viscous (1) force, or the moment about x0, of a composite body (bodies.py) on a Flow"""
+    from .core import sgrid
+    prog = body.program(a.D)
+    g = sgrid(a.p)
+    out = (C.c_double * 3)()
+    if which == 0:
+        check(lib().wl_pressure_force_bodyset(_x0(x0, a.D), ptr(a.p), C.byref(g), C.byref(prog), out, stream()))
+    else:
+        check(lib().wl_viscous_force_bodyset(_x0(x0, a.D), ptr(a.u), C.byref(g), float(a.nu), C.byref(prog), out, stream()))
+    return np.array(out[: a.D])
+
+
 def measure_(a, body, eps=1.0):
-    """measure!(a::Flow, body; ϵ) for a closed-form AutoBody   src/Body.jl:28-51"""
+    """measure!(a::Flow, body; ϵ) for a closed-form AutoBody, or a composite body of bodies.py (RigidMap leaves, set operations)
+    src/Body.jl:28-51"""
+    if _is_set(body):
+        from .core import ptr, sgrid, perdir_mask
+        prog = body.program(a.D)
+        g = sgrid(a.sigma)
+        check(lib().wl_measure_bodyset(ptr(a.sigma), ptr(a.mu0), ptr(a.mu1), ptr(a.V), C.byref(g), C.byref(prog), float(eps), int(a.exitBC),
+                                       perdir_mask(a.perdir), stream()))
+        a.has_body = True
+        return
     from ._lib import make_body
     from .core import ptr, sgrid, perdir_mask
     b = make_body(body, a.D)
@@ -23,6 +54,8 @@ def measure_(a, body, eps=1.0):
 
 def pressure_force(a, body):
     """pressure_force(p,df,body)   src/Metrics.jl:116-133 (Float64 sums; flow.f is not used as scratch)"""
+    if _is_set(body):
+        return _bodyset_force(0, a, body)
     from ._lib import make_body
     from .core import ptr, sgrid
     b = make_body(body, a.D)
@@ -34,6 +67,8 @@ def pressure_force(a, body):
 
 def viscous_force(a, body):
     """viscous_force(u,ν,df,body)   src/Metrics.jl:140-154"""
+    if _is_set(body):
+        return _bodyset_force(1, a, body)
     from ._lib import make_body
     from .core import ptr, sgrid
     b = make_body(body, a.D)
@@ -45,6 +80,8 @@ def viscous_force(a, body):
 
 def pressure_moment(x0, a, body):
     """pressure_moment(x₀,flow,body)   src/Metrics.jl:168-174"""
+    if _is_set(body):
+        return _bodyset_force(0, a, body, x0)
     from ._lib import make_body
     from .core import ptr, sgrid
     b = make_body(body, a.D)
@@ -57,6 +94,8 @@ def pressure_moment(x0, a, body):
 
 def viscous_moment(x0, a, body):
     """viscous_moment(x₀,flow,body)   src/Metrics.jl:182-188"""
+    if _is_set(body):
+        return _bodyset_force(1, a, body, x0)
     from ._lib import make_body
     from .core import ptr, sgrid
     b = make_body(body, a.D)
@@ -77,7 +116,8 @@ class Simulation:
             U = float(np.sqrt(sum(float(v) ** 2 for v in uBC)))                  # :100
         self.U, self.L, self.eps = float(U), float(L), eps
         self.flow = Flow(dims, uBC, dt=dt, nu=nu, g=g, u0=u0, perdir=perdir, exitBC=exitBC, lam=lam, T=T, duBC_dt=duBC_dt)   # :103
-        self.body = body          # None (NoBody) or a closed-form AutoBody: ("sphere", c, R) | ("cylinder", c, R, axis) | ("plane", point, normal) [+ velocity]
+        self.body = body          # None (NoBody), a closed-form AutoBody: ("sphere", c, R) | ("cylinder", c, R, axis) | ("plane", point, normal) [+ velocity],
+                                  # or a composite body of bodies.py (Body leaves under RigidMaps, set operations); setmap + remeasure moves it
         if body is not None:
             measure_(self.flow, body, eps=self.eps)                                                 # :104
         self.pois = MultiLevelPoisson(self.flow.p, self.flow.mu0, self.flow.sigma, perdir=perdir)   # :97,105
@@ -221,10 +261,25 @@ class FusedSimulation:
     def phase_(self, k):
         check(lib().wl_sim_phase(self._h, int(k), stream()))
 
+    def set_body(self, body, eps=1.0):
+        """store a composite body (bodies.py) and measure it on the device (measure!(sim), src/WaterLily.jl:146-149); afterwards
+        sim_step_(remeasure=True) remeasures the stored body — replace it with set_body(setmap(...)) or by assigning `.body`"""
+        assert self.has_body, "FusedSimulation was created with has_body=False"
+        self.body, self.eps = body, float(eps)
+        self.measure_bodyset_(body, eps)
+
+    def measure_bodyset_(self, body, eps=1.0):
+        """measure!(sim) for a composite body on the device + update!(pois)"""
+        prog = body.program(self.D)
+        check(lib().wl_sim_measure_bodyset(self._h, C.byref(prog), float(eps), stream()))
+
     def sim_step_(self, t_end=None, remeasure=False, max_steps=2**31 - 1):
         if t_end is None:
             if remeasure:
-                check(lib().wl_sim_update(self._h, stream()))
+                if getattr(self, "body", None) is not None:
+                    self.measure_bodyset_(self.body, self.eps)      # at t = sum(Δt): the stored body's current map
+                else:
+                    check(lib().wl_sim_update(self._h, stream()))
             self.mom_step_()
             return
         n = 0
@@ -300,7 +355,15 @@ class FusedSimulation:
         b = make_body(body, self.D)
         check(lib().wl_sim_measure_body(self._h, C.byref(b), float(eps), stream()))
 
+    def _bodyset_force(self, fn, body, x0=None):
+        prog = body.program(self.D)
+        out = (C.c_double * 3)()
+        check(fn(self._h, _x0(x0, self.D), C.byref(prog), out, stream()))
+        return np.array(out[: self.D])
+
     def pressure_force_body(self, body):
+        if _is_set(body):
+            return self._bodyset_force(lib().wl_sim_pressure_force_bodyset, body)
         from ._lib import make_body
         b = make_body(body, self.D)
         out = (C.c_double * 3)()
@@ -308,6 +371,8 @@ class FusedSimulation:
         return np.array(out[: self.D])
 
     def viscous_force_body(self, body):
+        if _is_set(body):
+            return self._bodyset_force(lib().wl_sim_viscous_force_bodyset, body)
         from ._lib import make_body
         b = make_body(body, self.D)
         out = (C.c_double * 3)()
@@ -327,10 +392,14 @@ class FusedSimulation:
 
     def pressure_moment_body(self, x0, body):
         """pressure_moment(x₀,sim)   src/Metrics.jl:167-174"""
+        if _is_set(body):
+            return self._bodyset_force(lib().wl_sim_pressure_force_bodyset, body, x0)
         return self._moment(lib().wl_sim_pressure_moment_body, x0, body)
 
     def viscous_moment_body(self, x0, body):
         """viscous_moment(x₀,sim)   src/Metrics.jl:181-188"""
+        if _is_set(body):
+            return self._bodyset_force(lib().wl_sim_viscous_force_bodyset, body, x0)
         return self._moment(lib().wl_sim_viscous_moment_body, x0, body)
 
     def total_moment_body(self, x0, body):

@@ -195,6 +195,20 @@ class SlabSimulation:
         c = (C.c_float * 3)(*[float(v) for v in center])
         check(lib().wl_sim_measure_sphere(self._h, c, float(R), float(eps), None))
 
+    def measure_bodyset_(self, body, eps=1.0):
+        """measure!(sim) for a composite body (bodies.py) in GLOBAL coordinates on the device + halos + update!(pois)"""
+        prog = body.program(self.D)
+        check(lib().wl_sim_measure_bodyset(self._h, C.byref(prog), float(eps), None))
+
+    def force_bodyset(self, which, body, x0=None):
+        """pressure (which 0) / viscous (1) force of a composite body, or its moment about x0: collective over the slabs"""
+        prog = body.program(self.D)
+        out = (C.c_double * 3)()
+        xx = None if x0 is None else (C.c_float * 3)(*([float(v) for v in x0] + [0.0] * (3 - self.D)))
+        fn = lib().wl_sim_pressure_force_bodyset if which == 0 else lib().wl_sim_viscous_force_bodyset
+        check(fn(self._h, xx, C.byref(prog), out, None))
+        return np.array(out[: self.D])
+
     def measure_body_(self, body, eps=1.0):
         from ._lib import make_body
         b = make_body(body, self.D)
