@@ -91,6 +91,12 @@ int wl_div(float* z, const float* u, const wl_grid* g, void* stream);           
 int wl_project(float* u, const float* L, const float* x, const wl_grid* g, void* stream); /* u[I,i] -= L[I,i]∂ᵢx :227-229 */
 /* CFL(a) :234-237 — writes σ=flux_out on the interior and returns min(Δt_max, 1/(max(σ over ALL cells)+5ν)) */
 int wl_cfl(const float* u, float* sigma, const wl_grid* g, float nu, float dt_max, float* host_dt, void* stream);
+/* sgs!(flow,u,t; νₜ=smagorinsky,S,Cs,Δ) src/util.jl:66-76 — the Smagorinsky–Lilly sub-grid-scale force added to f (= flow.f): S = S(I,u) on inside(σ)
+ * (src/Metrics.jl:42-44,140), νₜ(I) = (Cs·Δ)²·sqrt(S[I]:S[I]) (the docstring's code example, :62 — sqrt(S:S), not the sqrt(2S:S) of its prose: scale Cs by 2^¼ for
+ * that form), νₜ ≡ 0 on the ghost layer (a zero-initialised S buffer); then the nine (i,j) sweeps over inside_u(N,j) as one gather in the reference's order.
+ * sigma (= flow.σ) is scratch, as in the reference: its inside cells receive νₜ, its ghost cells what the reference's sweeps leave there.  At most two launches.
+ * 3-D single-domain grids only: a 2-D or z-slab wl_grid returns WL_EINVAL. */
+int wl_sgs(float* f, float* sigma, const float* u, const wl_grid* g, float Cs, float Delta, void* stream);
 
 /* ---- Poisson leaf operations: src/Poisson.jl --------------------------------------------------- */
 int wl_set_diag(float* D, float* iD, const float* L, const wl_grid* g, void* stream);   /* set_diag! :43-46 */
@@ -229,6 +235,12 @@ int wl_reset_process_options(void);
    NULL U1 keeps the boundary velocity; NULL a0 and a1 switches the forcing off. */
 int wl_sim_set_forcing(wl_sim* s, const float* U1, const float* a0, const float* a1);
 int wl_accelerate(float* r, const wl_grid* g, const float a[3], void* stream);   /* accelerate! for a uniform acceleration: r[I,i] += a_i */
+/* Built-in sub-grid-scale model of the composite: model 0 = off (default; the step is exactly the one without this call), 1 = Smagorinsky–Lilly.
+ * When on, wl_sim_mom_step, wl_sim_mom_steps and wl_sim_phase 1 and 3 do what mom_predict!/mom_correct! do with udf=sgs! (src/Flow.jl:191-193,206-208):
+ * wl_sgs after conv_diff! and before accelerate!, on u⁰ in the predictor and on the projected u in the corrector.  Both phases then take the staged sequence
+ * conv_diff! -> sgs! -> accelerate! -> BDIM! -> scale_u! -> BC! (r must exist when the model adds to it): the fused conv_diff!+BDIM! launch and what builds on it
+ * ("bcdefer", "tailfuse", "lazydt", the body hybrid) stand down.  WL_EINVAL for a 2-D or z-slab handle and for any other `model`. */
+int wl_sim_set_sgs(wl_sim* s, int model, float Cs, float Delta);
 int wl_sim_update(wl_sim* s, void* stream);             /* update!(pois) after μ₀ changed (measure!, src/WaterLily.jl:148) */
 int wl_sim_mom_step(wl_sim* s, void* stream);           /* mom_step!(flow,pois): appends Δt */
 /* n × mom_step! in one call — the loop of sim_step!(sim,t_end) without measure! (src/WaterLily.jl:136-139 with remeasure=false).  Same results as n calls of

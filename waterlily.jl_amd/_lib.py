@@ -100,6 +100,7 @@ SIGNATURES = {
     "wl_div": (i32, [P, P, G, P]),
     "wl_project": (i32, [P, P, P, G, P]),
     "wl_cfl": (i32, [P, P, G, f32, f32, C.POINTER(f32), P]),
+    "wl_sgs": (i32, [P, P, P, G, f32, f32, P]),
     "wl_set_diag": (i32, [P, P, P, G, P]),
     "wl_mult": (i32, [P, P, P, P, G, P]),
     "wl_residual": (i32, [P, P, P, P, P, P, G, P, P]),
@@ -140,6 +141,7 @@ SIGNATURES = {
     "wl_sim_update": (i32, [P, P]),
     "wl_sim_set_forcing": (i32, [P, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]),
     "wl_accelerate": (i32, [P, G, C.POINTER(f32), P]),
+    "wl_sim_set_sgs": (i32, [P, i32, f32, f32]),
     "wl_sim_mom_step": (i32, [P, P]),
     "wl_sim_mom_steps": (i32, [P, i32, P]),
     "wl_sim_dt": (i32, [P, C.POINTER(f32), i32]),

@@ -539,6 +539,8 @@ int wl_conv_diff(float* r, const float* u, float* Phi, const wl_grid* g, float n
 int wl_bdim(float* u, const float* u0, float* f, const float* V, const float* mu0, const float* mu1, const wl_grid* g, float dt, float pre, float post, void* st) {
   GRID_ARG(g); return wl::bdim(u, u0, f, V, mu0, mu1, G, dt, pre, post, wl_stream(st));
 }
+// sgs!(flow,u,t; νₜ=smagorinsky,S,Cs,Δ)   src/util.jl:66-76 — f = flow.f, sigma = flow.σ (scratch: receives νₜ)
+int wl_sgs(float* f, float* sigma, const float* u, const wl_grid* g, float Cs, float Delta, void* st) { GRID_ARG(g); return wl::sgs(f, sigma, u, G, Cs, Delta, wl_stream(st)); }
 int wl_scale_u(float* u, const wl_grid* g, float s, void* st) { GRID_ARG(g); return wl::scale_u(u, G, s, wl_stream(st)); }
 int wl_div(float* z, const float* u, const wl_grid* g, void* st) { GRID_ARG(g); return wl::div(z, u, G, wl_stream(st)); }
 int wl_project(float* u, const float* L, const float* x, const wl_grid* g, void* st) { GRID_ARG(g); return wl::project(u, L, x, G, wl_stream(st)); }

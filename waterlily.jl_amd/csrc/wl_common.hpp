@@ -254,6 +254,7 @@ bool conv_z_ok(const GridX& g, unsigned per);
 int conv_diff_z(float* f, const float* u_adv, const float* u0, const float* mu0, float* u_out, const GridX& g, float nu, int scheme, float dt, float pre, float post, hipStream_t s);
 int bdim(float* u, const float* u0, float* f, const float* V, const float* mu0, const float* mu1, const GridX& g, float dt, float pre, float post, hipStream_t s);
 int accelerate(float* r, const GridX& g, const float* a, hipStream_t s);
+int sgs(float* f, float* sigma, const float* u, const GridX& g, float Cs, float Delta, hipStream_t s);   // sgs! with the Smagorinsky–Lilly νₜ (wl_sgs.hip): 3-D single domain, else WL_EINVAL
 int bc_vec_fn(float* a, const float* Ub, const GridX& g, int saveexit, unsigned per, hipStream_t s);
 int add_field(float* r, const float* gfield, size_t n, hipStream_t s);
 int meanflow_update(float* P, float* U, float* UU, const float* p, const float* u, const GridX& g, float e, hipStream_t s);

@@ -265,6 +265,12 @@ struct wl_sim {
   bool forcing = false;      // uniform g(i,t)+dU(i,t)/dt supplied by the host for the current step (accelerate!, src/Flow.jl:69-73)
   float acc0[3] = {0, 0, 0}, acc1[3] = {0, 0, 0};   // at t₀ (predictor) and t₁ (corrector)
   float* us = nullptr;       // spare velocity array: the fused corrector writes here, then u and us trade places
+  // sgs! as the step's udf (wl_sim_set_sgs; src/Flow.jl:191-193,206-208 with udf=sgs!, src/util.jl:66-76): the model adds to r = conv_diff!'s output, so both
+  // phases take the staged sequence conv_diff! -> sgs! -> accelerate! -> BDIM! -> scale_u! -> BC!; everything that assumes the fused conv_diff!+BDIM! launch
+  // ran (bcdefer, tailfuse, lazydt, the body hybrid) stands down, as it does for `forcing`
+  int sgs_model = 0;         // 0 off, 1 Smagorinsky–Lilly
+  float sgs_Cs = 0.f, sgs_Delta = 1.f;
+  int sgs_udf(const float* uadv, hipStream_t s) { return sgs_model ? wl::sgs(f, sigma, uadv, G, sgs_Cs, sgs_Delta, s) : 0; }   // udf!(a,sgs!,uadv,t)
   std::vector<float> dt;
   bool own_mg = true;        // false: the multigrid handle belongs to the caller (wl_sim_create_on)
   ~wl_sim() { if (u_pending && comm && comm->cs) (void)hipStreamSynchronize(comm->cs); if (own_mg) delete mg; if (own) (void)hipFree(own); if (exit_sc) (void)hipFree(exit_sc); if (farmask) (void)hipFree(farmask); if (mnear) (void)hipFree(mnear); if (mneedf) (void)hipFree(mneedf); if (mm0var) (void)hipFree(mm0var); }
@@ -322,7 +328,7 @@ struct wl_sim {
   bool use_tailfuse = false;
   const float* proj_pending = nullptr;
   bool tailfuse_ok() const {
-    return use_tailfuse && fold_ok(3) && us && !d.has_body && !forcing && !store_f && !use_convz && !u_pending && mg->lv[0].cl.on && !mg->lv[0].part &&
+    return use_tailfuse && fold_ok(3) && us && !d.has_body && !forcing && !sgs_model && !store_f && !use_convz && !u_pending && mg->lv[0].cl.on && !mg->lv[0].part &&
            wl::conv_proj_ok(G, d.perdir_mask);
   }
   bool use_convz = false;    // z-marching conv_diff! (each flux once): bit-identical but measured 6 % SLOWER than the gather kernel at 512³ (opt-in)
@@ -341,7 +347,7 @@ struct wl_sim {
   int near_box[4] = {0, -1, 0, -1};   // {b0,b1,k0,k1}: bounding box of the near workgroups
   int dirty_z[2] = {0, -1};           // first / last plane with any near / f-keeping / μ₀-loading workgroup (the other planes are NoBody planes)
   bool use_hybrid = true;
-  bool hybrid_ok() const { return d.has_body && use_hybrid && mask_valid && mnear && us && !comm && !forcing && !d.exitBC; }
+  bool hybrid_ok() const { return d.has_body && use_hybrid && mask_valid && mnear && us && !comm && !forcing && !sgs_model && !d.exitBC; }
   int refresh_body_mask(hipStream_t s) {
     if (!d.has_body || !mu1 || !V) return 0;
     if (!farmask) WL_HIP(hipMalloc((void**)&farmask, wl::body_mask_bytes(G)));
@@ -402,7 +408,7 @@ struct wl_sim {
       return bc_u(s);
     }
     bool fused_conv = false;
-    if (us && !d.has_body && !forcing) {   // conv_diff!(f,u⁰) + BDIM! in one launch (u⁰ is the advecting field, u the output)
+    if (us && !d.has_body && !forcing && !sgs_model) {   // conv_diff!(f,u⁰) + BDIM! in one launch (u⁰ is the advecting field, u the output)
       ProfScope pc(WL_PROF_CONVDIFF, s);
       if (use_convz && wl::conv_z_ok(G, d.perdir_mask)) {
         WL_TRY(sync_u(s));
@@ -411,6 +417,7 @@ struct wl_sim {
       } else { WL_TRY(conv_fused(u0, u, 0.f, 1.f, s, !(in_step && !store_f), dt_dev)); fused_conv = true; }
     } else {
       { ProfScope pc(WL_PROF_CONVDIFF, s); WL_TRY(conv_only(u0, s)); }
+      WL_TRY(sgs_udf(u0, s));                                                              // udf!(a,udf,a.u⁰,t₀): the model sees u⁰ (a.u is zeroed)
       if (forcing) WL_TRY(wl::accelerate(f, G, acc0, s));                                  // accelerate!(f,t₀,g,uBC)
       WL_TRY(bdim_step(0.f, 1.f, s));   // scale_u!(a,0) folded (pre=0)
     }
@@ -424,7 +431,7 @@ struct wl_sim {
       std::swap(u, us);
       return bc_u(s);
     }
-    if (us && !d.has_body && !forcing) {   // the advecting field is u itself: write the new u to the spare array and swap
+    if (us && !d.has_body && !forcing && !sgs_model) {   // the advecting field is u itself: write the new u to the spare array and swap
       bool fused_conv = false;
       { ProfScope pc(WL_PROF_CONVDIFF, s);
         if (use_convz && wl::conv_z_ok(G, d.perdir_mask)) {
@@ -437,6 +444,7 @@ struct wl_sim {
       return fused_conv ? bc_u_or_defer(true, s) : bc_u(s);
     }
     { ProfScope pc(WL_PROF_CONVDIFF, s); WL_TRY(conv_only(u, s)); }
+    WL_TRY(sgs_udf(u, s));                                                                 // udf!(a,udf,a.u,t): the model sees the projected u
     if (forcing) WL_TRY(wl::accelerate(f, G, acc1, s));                                    // accelerate!(f,t₁,g,uBC)
     WL_TRY(bdim_step(1.f, 0.5f, s));  // scale_u!(a,0.5) folded (post)
     return bc_u(s);
@@ -579,7 +587,7 @@ struct wl_sim {
   bool use_lazydt = true, dt_pending = false;
   hipEvent_t ev_dt = nullptr;
   bool lazydt_ok() const {      // the next predictor will be the flux-once tiled launch on the single domain
-    return use_lazydt && in_step && !comm && us && !d.has_body && !forcing && !use_convz && !d.exitBC && !d.perdir_mask && !store_f && wl::conv_flux_on() &&
+    return use_lazydt && in_step && !comm && us && !d.has_body && !forcing && !sgs_model && !use_convz && !d.exitBC && !d.perdir_mask && !store_f && wl::conv_flux_on() &&
            wl::conv_tile_ok(G, d.perdir_mask, G.k1 - G.k0) && mg->lv[0].cl.on;
   }
   int cfl(hipStream_t s, bool more_follow = false) {                                     // CFL :234-237
@@ -893,6 +901,15 @@ int wl_sim_set_forcing(wl_sim* s, const float* U1, const float* a0, const float*
   if (U1) for (int c = 0; c < D; c++) s->d.uBC[c] = U1[c];
   s->forcing = a0 != nullptr || a1 != nullptr;
   for (int c = 0; c < 3; c++) { s->acc0[c] = (a0 && c < D) ? a0[c] : 0.f; s->acc1[c] = (a1 && c < D) ? a1[c] : 0.f; }
+  return 0;
+}
+int wl_sim_set_sgs(wl_sim* s, int model, float Cs, float Delta) {
+  WL_CHECK(s, "null wl_sim"); WL_CHECK(model == 0 || model == 1, "wl_sim_set_sgs: model must be 0 (off) or 1 (Smagorinsky-Lilly)");
+  if (model) {
+    if (s->d.D != 3) { wl_set_error("wl_sim_set_sgs: the Smagorinsky model is built for 3-D flows only"); return WL_EINVAL; }
+    if (s->comm) { wl_set_error("wl_sim_set_sgs: z-slab handles are not supported (single domain only)"); return WL_EINVAL; }
+  }
+  s->sgs_model = model; s->sgs_Cs = Cs; s->sgs_Delta = Delta;
   return 0;
 }
 int wl_accelerate(float* r, const wl_grid* g, const float* a, void* st) {

@@ -1,5 +1,6 @@
 """Flow — host-side mirror of /root/reference/src/Flow.jl over the HIP C ABI."""
 import ctypes as C
+import inspect
 
 import numpy as np
 
@@ -34,6 +35,33 @@ def CFL(a, dt_max=10):
     g = sgrid(a.sigma)
     check(lib().wl_cfl(ptr(a.u), ptr(a.sigma), C.byref(g), float(a.nu), float(dt_max), C.byref(out), stream()))
     return np.float32(out.value)
+
+
+def sgs_(a, u, Cs, Delta):
+    """sgs!(flow,u,t; νₜ=smagorinsky,S,Cs,Δ)   src/util.jl:66-76 — the Smagorinsky–Lilly force of the velocity `u` added to a.f;
+    νₜ = (Cs·Δ)²·sqrt(S:S) (the docstring's code example, :62).  a.sigma is scratch, as in the reference.  3-D only."""
+    g = vgrid(u)
+    check(lib().wl_sgs(ptr(a.f), ptr(a.sigma), ptr(u), C.byref(g), float(Cs), float(Delta), stream()))
+
+
+def sgs(flow, u, t, *, Cs, Delta, **_):
+    """`sgs_` in the shape of a udf: mom_step_(a, b, udf=sgs, Cs=0.17, Delta=1.0) — sim_step!(sim; udf=sgs!, νₜ=smagorinsky, S, Cs, Δ)"""
+    sgs_(flow, u, Cs, Delta)
+
+
+def udf_(a, udf, u, t, **kw):
+    """udf!(flow,udf,u,t; kwargs...)   src/Flow.jl:246-257 — `u` is the velocity the convective flux is evaluated on in that phase.
+    A udf that takes three positional arguments is called as udf(flow,u,t; kw...), any other as udf(flow,t; kw...) (`applicable`, :257);
+    parameters with a default count as keywords."""
+    if udf is None:
+        return
+    par = inspect.signature(udf).parameters.values()
+    pos = (inspect.Parameter.POSITIONAL_ONLY, inspect.Parameter.POSITIONAL_OR_KEYWORD)
+    three = any(q.kind is inspect.Parameter.VAR_POSITIONAL for q in par) or sum(q.kind in pos and q.default is q.empty for q in par) >= 3
+    if three:
+        udf(a, u, t, **kw)
+    else:
+        udf(a, t, **kw)
 
 
 class Flow:
@@ -99,9 +127,10 @@ def _times(a):
     return np.float32(t1 - a.dt[-1]), t1
 
 
-def mom_predict_(a, t0=0.0, t1=0.0):
-    """mom_predict!(a,t₀,t₁)   src/Flow.jl:190-196"""
+def mom_predict_(a, t0=0.0, t1=0.0, udf=None, **kw):
+    """mom_predict!(a,t₀,t₁;udf,kwargs...)   src/Flow.jl:190-196"""
     conv_diff_(a.f, a.u0, a.sigma, a.lam, nu=a.nu, perdir=a.perdir)
+    udf_(a, udf, a.u0, t0, **kw)                                                # advect with u⁰ (a.u is zeroed by scale_u!)
     core.accelerate_(a.f, float(t0), a.g, a.uBC, a.duBC_dt)
     BDIM_(a)
     BC_(a.u, a.uBC, a.exitBC, a.perdir, float(t1))
@@ -109,9 +138,10 @@ def mom_predict_(a, t0=0.0, t1=0.0):
         exitBC_(a.u, a.u0, a.dt[-1])
 
 
-def mom_correct_(a, t=0.0):
-    """mom_correct!(a,t)   src/Flow.jl:205-210"""
+def mom_correct_(a, t=0.0, udf=None, **kw):
+    """mom_correct!(a,t;udf,kwargs...)   src/Flow.jl:205-210"""
     conv_diff_(a.f, a.u, a.sigma, a.lam, nu=a.nu, perdir=a.perdir)
+    udf_(a, udf, a.u, t, **kw)                                                  # advect with the projected a.u
     core.accelerate_(a.f, float(t), a.g, a.uBC, a.duBC_dt)
     BDIM_(a)
     scale_u_(a, 0.5)
@@ -131,13 +161,13 @@ def mom_project_(a, b, w, t=0.0):
     BC_(a.u, a.uBC, a.exitBC, a.perdir, float(t))
 
 
-def mom_step_(a, b):
-    """mom_step!(a::Flow,b::AbstractPoisson)   src/Flow.jl:156-167 — written on the leaf operations, line for line."""
+def mom_step_(a, b, udf=None, **kw):
+    """mom_step!(a::Flow,b::AbstractPoisson;udf,kwargs...)   src/Flow.jl:156-167 — written on the leaf operations, line for line."""
     check(lib().wl_d2d(ptr(a.u0), ptr(a.u), 4 * a.u.numel(), stream()))        # a.u⁰ .= a.u
     scale_u_(a, 0)
     t0, t1 = _times(a)
-    mom_predict_(a, t0, t1)
+    mom_predict_(a, t0, t1, udf=udf, **kw)
     mom_project_(a, b, 1, t1)
-    mom_correct_(a, t1)
+    mom_correct_(a, t1, udf=udf, **kw)
     mom_project_(a, b, 0.5, t1)
     a.dt.append(CFL(a))

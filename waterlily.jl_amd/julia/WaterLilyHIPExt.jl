@@ -339,12 +339,22 @@ function set_forcing!(sim, a::HFlow{D}) where {D}
     acc(t) = pad3(ntuple(i -> (a.g === nothing ? 0f0 : Float32(a.g(i, x0, t))) + dUdt(a.uBC, i, x0, t), D))
     chk(ccall((:wl_sim_set_forcing, libwlhip), Cint, (Ptr{Cvoid}, Ref{NTuple{3,Cfloat}}, Ref{NTuple{3,Cfloat}}, Ref{NTuple{3,Cfloat}}), sim, Ref(U1), Ref(acc(t0)), Ref(acc(t1))))
 end
+# LES: the one udf that does cross the C ABI is the library's built-in.  `Smagorinsky()` stands in for the docstring's closure
+# smagorinsky(I;S,Cs,Δ) = (Cs*Δ)^2*sqrt(dot(S[I,:,:],S[I,:,:])) (src/util.jl:62):
+#     sim_step!(sim; udf=WaterLily.sgs!, νₜ=Smagorinsky(), Cs=0.17f0, Δ=1f0)
+# sets the model on the handle (wl_sim_set_sgs) and keeps the composite path — sgs! after conv_diff!, before accelerate!, on u⁰ in the predictor
+# and on the projected u in the corrector (src/Flow.jl:191-193,206-208).  No `S` buffer is needed (the kernels never materialise the tensor).
+# A 2-D flow raises the library's WL_EINVAL: never a silently unmodelled step.  Any other udf keeps the route below.
+# (This method has been desk-checked only: no Julia runtime was available where the library is built and tested.)
+struct Smagorinsky end
 function mom_step!(a::HFlow{D}, b::HipMultiLevel; udf=nothing, kwargs...) where {D}
     N = size(a.p) .- 2; tnow = sum(a.Δt)
-    if udf !== nothing || !(uniform_in_x(a.uBC, D, N, tnow) && uniform_in_x(a.g, D, N, tnow))
+    les = udf === WaterLily.sgs! && get(kwargs, :νₜ, nothing) isa Smagorinsky
+    if (udf !== nothing && !les) || !(uniform_in_x(a.uBC, D, N, tnow) && uniform_in_x(a.g, D, N, tnow))
         return invoke(mom_step!, Tuple{AbstractFlow,AbstractPoisson}, a, b; udf, kwargs...)      # position-dependent closures: the reference's own mom_step! over the leaf methods
     end
     sim = composite!(a, b)
+    chk(ccall((:wl_sim_set_sgs, libwlhip), Cint, (Ptr{Cvoid}, Cint, Cfloat, Cfloat), sim, Cint(les), les ? Float32(kwargs[:Cs]) : 0f0, les ? Float32(kwargs[:Δ]) : 1f0))
     set_forcing!(sim, a)
     chk(ccall((:wl_sim_set_dt_last, libwlhip), Cint, (Ptr{Cvoid}, Cfloat), sim, a.Δt[end]))    # the host owns flow.Δt (src/Flow.jl:127)
     chk(ccall((:wl_sim_mom_step, libwlhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), sim, C_NULL))

@@ -125,16 +125,16 @@ class Simulation:
     def sim_time(self):
         return float(self.flow.time()) * self.U / self.L                          # :117
 
-    def sim_step_(self, t_end=None, remeasure=True, max_steps=2**31 - 1):
-        """sim_step!(sim[,t_end];remeasure,max_steps)   :128-139"""
+    def sim_step_(self, t_end=None, remeasure=True, max_steps=2**31 - 1, udf=None, **kw):
+        """sim_step!(sim[,t_end];remeasure,max_steps,udf,kwargs...)   :128-139 — `udf` and its keywords go to mom_step! (eg. udf=sgs, Cs=0.17, Delta=1)"""
         if t_end is None:
             if remeasure:
                 self.measure_()
-            mom_step_(self.flow, self.pois)
+            mom_step_(self.flow, self.pois, udf=udf, **kw)
             return
         steps0 = len(self.flow.dt)
         while self.sim_time() < t_end and len(self.flow.dt) - steps0 < max_steps:
-            self.sim_step_(remeasure=remeasure)
+            self.sim_step_(remeasure=remeasure, udf=udf, **kw)
 
     def measure_(self, body=None):
         """measure!(sim): measure!(flow,body) + update!(pois)   :146-149 (quirk Q3: runs every step when remeasure=true; NoBody => only
@@ -257,6 +257,14 @@ class FusedSimulation:
                 self.mom_step_()
             return
         check(lib().wl_sim_mom_steps(self._h, int(n), stream()))
+
+    def set_sgs(self, Cs, Delta=1.0):
+        """the built-in Smagorinsky–Lilly model as the step's udf (sim_step!(sim; udf=sgs!, νₜ=smagorinsky, S, Cs, Δ), src/util.jl:45-76):
+        set_sgs(0.17, 1.0) switches it on for every following step, set_sgs(None) off (the default).  3-D single-domain flows."""
+        if Cs is None:
+            check(lib().wl_sim_set_sgs(self._h, 0, 0.0, 1.0))
+        else:
+            check(lib().wl_sim_set_sgs(self._h, 1, float(Cs), float(Delta)))
 
     def phase_(self, k):
         check(lib().wl_sim_phase(self._h, int(k), stream()))
