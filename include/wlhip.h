@@ -220,6 +220,11 @@ int wl_sim_init_flow(wl_sim* s, void* stream);          /* BC!(u), u⁰=u, μ₀
    "tailfuse"[0] wl_sim_mom_step: the first projection's tail (u −= L∇x, BC!) is evaluated by the corrector's conv_diff! loader; the projected predictor
        velocity is never written (whole tiles, single domain, tuple U, no periodic direction / exit / body; results identical; measured: no gain, hence off).
        wl_sim_phase always keeps the tail launch.
+   "pdefer"[1] wl_sim_mom_step / wl_sim_mom_steps: a projection tail whose p = x/Δt would be read next by the fused projection head of the same call does not
+       store it; that head takes the solver's scaled x and divides on load (same roundings in the same order: identical bits; 4 B/cell less per tail).  The
+       predictor's tail when the corrector's head will be fused, the corrector's when another step follows inside wl_sim_mom_steps; the last tail of a call always
+       stores.  Not with the sgs model, forcing, a body, slabs, exitBC, a periodic direction or "store_f".  The pressure may end a call in the other of the handle's
+       two pressure arrays: wl_sim_field("p") reports the one that holds it; a caller-owned p always receives it (there a single step stores both times).
    "convf"[1] the tiled conv_diff!+BDIM! evaluates every face flux once (wl_convf.hip); 0: the two-cells-per-thread kernel that re-evaluates upper faces
    "convt_min"[2048] tile-planes below which "convt" leaves the launch to the plane kernel (tests: 0)
    "xdefer"[1] pair smoother: the V-cycle's x += ω·x_c↓ is applied by kernel B together with its own increment (x makes one round trip per smooth!)

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "wl_common.hpp"
+#include "wl_pdefer.hpp"
 #include "wl_bcfold.hpp"
 #include "wl_conv_cell.hpp"
 
@@ -28,14 +29,14 @@ __global__ void k_scale(float* __restrict__ a, float s, size_t n) {
   for (size_t q = (size_t)blockIdx.x * WL_BLOCK + threadIdx.x; q < n; q += (size_t)gridDim.x * WL_BLOCK) a[q] = a[q] * s;
 }
 __global__ void k_divs(float* __restrict__ a, float s, size_t n) {
-  for (size_t q = (size_t)blockIdx.x * WL_BLOCK + threadIdx.x; q < n; q += (size_t)gridDim.x * WL_BLOCK) a[q] = a[q] / s;
+  for (size_t q = (size_t)blockIdx.x * WL_BLOCK + threadIdx.x; q < n; q += (size_t)gridDim.x * WL_BLOCK) a[q] = wl_unscale(a[q], s);
 }
 // out = in / s (out ≠ in): the p = x/Δt half of mom_project!'s tail when the velocity half is evaluated by the corrector's loader (wl_convf.hip, PROJ)
 __global__ void k_divs_to4(float4* __restrict__ out, const float4* __restrict__ in, float s, size_t n4) {
-  for (size_t q = (size_t)blockIdx.x * WL_BLOCK + threadIdx.x; q < n4; q += (size_t)gridDim.x * WL_BLOCK) { const float4 v = in[q]; out[q] = make_float4(v.x / s, v.y / s, v.z / s, v.w / s); }
+  for (size_t q = (size_t)blockIdx.x * WL_BLOCK + threadIdx.x; q < n4; q += (size_t)gridDim.x * WL_BLOCK) { const float4 v = in[q]; out[q] = make_float4(wl_unscale(v.x, s), wl_unscale(v.y, s), wl_unscale(v.z, s), wl_unscale(v.w, s)); }
 }
 __global__ void k_divs_to(float* __restrict__ out, const float* __restrict__ in, float s, size_t n) {
-  for (size_t q = (size_t)blockIdx.x * WL_BLOCK + threadIdx.x; q < n; q += (size_t)gridDim.x * WL_BLOCK) out[q] = in[q] / s;
+  for (size_t q = (size_t)blockIdx.x * WL_BLOCK + threadIdx.x; q < n; q += (size_t)gridDim.x * WL_BLOCK) out[q] = wl_unscale(in[q], s);
 }
 __global__ void k_red_sum(const float* __restrict__ a, size_t n, double* __restrict__ part) {
   double acc = 0.0;

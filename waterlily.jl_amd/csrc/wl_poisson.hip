@@ -7,6 +7,7 @@
 
 #include "wl_common.hpp"
 #include "wl_bcfold.hpp"
+#include "wl_pdefer.hpp"
 
 namespace {
 
@@ -140,7 +141,8 @@ __global__ void k_div_residual(GridX g, float* __restrict__ z, float* __restrict
 __device__ __forceinline__ int wl_enc_f(float v) { const int b = __float_as_int(v); return b >= 0 ? b : (b ^ 0x7FFFFFFF); }
 __device__ __forceinline__ float wl_dec_f(int k) { return __int_as_float(k >= 0 ? k : (k ^ 0x7FFFFFFF)); }
 // mom_project! tail (src/Flow.jl:227-230): u[I,i] -= L[I,i]·∂ᵢx ; p_out = x/dt (ALL cells), p_out ≠ x
-template <int D, int CL>
+// SP = 0: p_out is not stored (skip_p, wl_pdefer.hpp — the next fused head divides on load, wl_resjac_body.inc); the store and its division are compiled out
+template <int D, int CL, int SP = 1>
 __global__ void k_project_unscale(GridX g, float* __restrict__ u, const float* __restrict__ L, const float* __restrict__ x, float* __restrict__ pout, float dt, wl::ConstL cl, int zchunk,
                                   int p0, int p1, BcFold bc, int lin) {   // local planes [p0,p1) of this launch; bc.on: BC!(u,U) folded into the stores (wl_bcfold.hpp); lin: linear block order (wl_tile_lin)
   if (bc.go && !(*bc.go > 0.f)) return;   // queued before the host knew whether the solve had converged: it had not (0), or the solve is discarded (−1)
@@ -154,7 +156,7 @@ __global__ void k_project_unscale(GridX g, float* __restrict__ u, const float* _
   const float lxc = CL ? wl::wl_cl_coef(i + 1, g.nx, cl.c[0]) : 0.f, lyc = CL ? wl::wl_cl_coef(j + 1, g.ny, cl.c[1]) : 0.f;
   for (int k = ks; k < ke; k++, o += g.sz) {
     const float xc = x[o];
-    pout[o] = xc / dt;
+    if (SP) pout[o] = wl_unscale(xc, dt);
     bool in = inij;
     if (D == 3) in = in && k >= g.k0 && k < g.k1;
     if (in) {
@@ -196,7 +198,7 @@ __global__ void k_project_cfl(GridX g, float* __restrict__ uout, const float* __
     }
     for (int k = ks; k < ke; k++, o += g.sz) {
       const float xkp = (D == 3 && k + 1 < g.nz) ? x[o + g.sz] : 0.f;
-      pout[o] = xc / dt;
+      pout[o] = wl_unscale(xc, dt);
       bool in = inij;
       if (D == 3) in = in && k >= g.k0 && k < g.k1;
       float sg;
@@ -250,6 +252,7 @@ __device__ __forceinline__ bool pl_pair(const GridX& g, long& m, int& k, int p0)
   return m < g.sz;
 }
 static inline unsigned pl_grid(const GridX& g, int nplanes) { const long np2 = (g.sz / 2 + WL_BLOCK - 1) / WL_BLOCK; return (unsigned)((((np2 + 7) >> 3) << 3) * nplanes); }
+template <int SP>      // SP = 0: p_out is not stored (skip_p, wl_pdefer.hpp)
 __global__ void __launch_bounds__(WL_BLOCK) k_project_unscale2(GridX g, float* __restrict__ u, const float* __restrict__ x, float* __restrict__ pout, float dt, wl::ConstL cl,
                                                                   int p0, int p1, BcFold bc) {
   if (bc.go && !(*bc.go > 0.f)) return;
@@ -258,7 +261,7 @@ __global__ void __launch_bounds__(WL_BLOCK) k_project_unscale2(GridX g, float* _
   const int j = (int)(m / g.nx), i0 = (int)(m - (long)j * g.nx);
   const long o = m + (long)k * g.sz;
   const float2 xc = pl_ld2(x, o);
-  pl_st2(pout, o, make_float2(xc.x / dt, xc.y / dt));
+  if (SP) pl_st2(pout, o, make_float2(wl_unscale(xc.x, dt), wl_unscale(xc.y, dt)));
   if (!(j >= 1 && j <= g.ny - 2 && k >= g.k0 && k < g.k1)) return;
   const bool in0 = i0 >= 1, in1 = i0 + 1 <= g.nx - 2;                 // (i0 is even: i0 <= nx-2 always; cell 0 is a ghost only at i0 == 0)
   const float xl = in0 ? x[o - 1] : 0.f;
@@ -277,6 +280,7 @@ __global__ void __launch_bounds__(WL_BLOCK) k_project_unscale2(GridX g, float* _
   else if (in0) { u[o] = va[0]; u[g.cs + o] = va[1]; u[2 * g.cs + o] = va[2]; }
   else if (in1) { u[o + 1] = vb[0]; u[g.cs + o + 1] = vb[1]; u[2 * g.cs + o + 1] = vb[2]; }
 }
+template <int SP>      // SP = 0: p_out is not stored (skip_p, wl_pdefer.hpp)
 __global__ void __launch_bounds__(WL_BLOCK) k_project_cfl2(GridX g, float* __restrict__ uout, const float* __restrict__ uin, const float* __restrict__ x, float* __restrict__ pout,
                                                               float* __restrict__ sigma, float dt, wl::ConstL cl, int kfirst, int klast, float* __restrict__ pmax, int p0, int p1,
                                                               int store_sigma, BcFold bc) {
@@ -287,7 +291,7 @@ __global__ void __launch_bounds__(WL_BLOCK) k_project_cfl2(GridX g, float* __res
     const int j = (int)(m / g.nx), i0 = (int)(m - (long)j * g.nx);
     const long o = m + (long)k * g.sz;
     const float2 xc = pl_ld2(x, o);
-    pl_st2(pout, o, make_float2(xc.x / dt, xc.y / dt));
+    if (SP) pl_st2(pout, o, make_float2(wl_unscale(xc.x, dt), wl_unscale(xc.y, dt)));
     const bool row = j >= 1 && j <= g.ny - 2 && k >= g.k0 && k < g.k1;
     const bool in0 = row && i0 >= 1, in1 = row && i0 + 1 <= g.nx - 2;
     const bool want = k >= kfirst && k < klast;
@@ -1130,13 +1134,22 @@ static int tail_pair_bits() { static const int v = wl_exp_int("WL_TAIL_PAIR", 2)
 static int tail_pair() { return tail_pair_bits() & 1; }
 static int tail_lin(int bit) { static const int v = wl_exp_int("WL_TAIL_LIN", 1); return (v >> bit) & 1; }
 int project_unscale(float* u, const float* L, const float* x, float* pout, const GridX& g, float dt, const ConstL& cl, hipStream_t s, const BcFold* fold) {
+  return project_unscale(u, L, x, pout, g, dt, cl, s, fold, false);
+}
+int project_unscale(float* u, const float* L, const float* x, float* pout, const GridX& g, float dt, const ConstL& cl, hipStream_t s, const BcFold* fold, bool skip_p) {
   const int lin = tail_lin(0) && g.D == 3;
   const int zc = lin ? 1 : wl_march_chunk(g, g.nz);
   BcFold bc{0, {0.f, 0.f, 0.f}};
   if (fold && fold->on && g.D == 3 && g.nz == g.gnz && g.nx >= 6 && g.ny >= 6 && g.nz >= 6) bc = *fold;
   bc.go = fold ? fold->go : nullptr;
   if (tail_pair() && lin && cl.on && (g.nx & 1) == 0 && g.k0 >= 1) {   // two cells per thread (k_project_unscale2): x[o−sz] of plane 0 is never read (k0 >= 1)
-    hipLaunchKernelGGL(k_project_unscale2, dim3(pl_grid(g, g.nz)), dim3(WL_BLOCK), 0, s, g, u, x, pout, dt, cl, 0, g.nz, bc);
+    if (skip_p) hipLaunchKernelGGL(k_project_unscale2<0>, dim3(pl_grid(g, g.nz)), dim3(WL_BLOCK), 0, s, g, u, x, pout, dt, cl, 0, g.nz, bc);
+    else hipLaunchKernelGGL(k_project_unscale2<1>, dim3(pl_grid(g, g.nz)), dim3(WL_BLOCK), 0, s, g, u, x, pout, dt, cl, 0, g.nz, bc);
+    WL_LAUNCH_CHECK(); return 0;
+  }
+  if (skip_p) {   // the store-free form exists for the 3-D constant-coefficient kernel (the only levels a fused head follows)
+    if (!(g.D == 3 && cl.on)) { wl_set_error("project_unscale: the tail without the p store needs a 3-D constant-coefficient level"); return WL_EINVAL; }
+    hipLaunchKernelGGL((k_project_unscale<3, 1, 0>), wl_plane_grid(g, wl_march_slots(g.nz, zc)), dim3(WL_BLOCK), 0, s, g, u, L, x, pout, dt, cl, zc, 0, g.nz, bc, lin);
     WL_LAUNCH_CHECK(); return 0;
   }
   DSEL2(g.D, cl.on, k_project_unscale, wl_plane_grid(g, wl_march_slots(g.nz, zc)), dim3(WL_BLOCK), 0, s, g, u, L, x, pout, dt, cl, zc, 0, g.nz, bc, lin);
@@ -1171,6 +1184,10 @@ int decide_converged(const RedWs& ws, double r1tol, double rinftol, double ninsi
 bool project_cfl_pair_path(const GridX& g, const ConstL& cl) { return (tail_pair_bits() & 2) && g.D == 3 && cl.on && (g.nx & 1) == 0 && g.k0 >= 1 && g.k1 <= g.nz - 1; }
 // projection tail + CFL's σ and max(σ) -> ws.res_f[slot_f]; u_out must not alias u_in
 int project_cfl(float* uout, const float* uin, const float* L, const float* x, float* pout, float* sigma, const GridX& g, float dt, const ConstL& cl, const RedWs& ws, int slot_f, hipStream_t s, int store_sigma, const BcFold* fold) {
+  return project_cfl(uout, uin, L, x, pout, sigma, g, dt, cl, ws, slot_f, s, store_sigma, fold, false);
+}
+int project_cfl(float* uout, const float* uin, const float* L, const float* x, float* pout, float* sigma, const GridX& g, float dt, const ConstL& cl, const RedWs& ws, int slot_f, hipStream_t s, int store_sigma, const BcFold* fold,
+                bool skip_p) {
   if (uout == uin) { wl_set_error("project_cfl: output aliases input"); return WL_EINVAL; }
   int kfirst = 0, klast = 1;
   if (g.D == 3) { kfirst = (g.gk + g.k0 == 1) ? g.k0 - 1 : g.k0; klast = (g.gk + g.k1 == g.gnz - 1) ? g.k1 + 1 : g.k1; }
@@ -1179,9 +1196,11 @@ int project_cfl(float* uout, const float* uin, const float* L, const float* x, f
   bc.go = fold ? fold->go : nullptr;
   if (bc.go && !project_cfl_pair_path(g, cl)) { wl_set_error("project_cfl: a tail queued ahead of the convergence read needs the two-cells-per-thread form"); return WL_EINVAL; }
   if (fold && fold->usub && !(bc.on && project_cfl_pair_path(g, cl))) { wl_set_error("project_cfl: deferred BC! needs the folded two-cells-per-thread tail"); return WL_EINVAL; }
+  if (skip_p && !project_cfl_pair_path(g, cl)) { wl_set_error("project_cfl: the tail without the p store needs the two-cells-per-thread form"); return WL_EINVAL; }
   if (project_cfl_pair_path(g, cl)) {   // two cells per thread, linear order (k_project_cfl2)
     hipLaunchKernelGGL(k_enc_init, dim3(1), dim3(WL_ENC_SLOTS), 0, s, reinterpret_cast<int*>(ws.pm));
-    hipLaunchKernelGGL(k_project_cfl2, dim3(pl_grid(g, g.nz)), dim3(WL_BLOCK), 0, s, g, uout, uin, x, pout, sigma, dt, cl, kfirst, klast, ws.pm, 0, g.nz, store_sigma, bc);
+    if (skip_p) hipLaunchKernelGGL(k_project_cfl2<0>, dim3(pl_grid(g, g.nz)), dim3(WL_BLOCK), 0, s, g, uout, uin, x, pout, sigma, dt, cl, kfirst, klast, ws.pm, 0, g.nz, store_sigma, bc);
+    else hipLaunchKernelGGL(k_project_cfl2<1>, dim3(pl_grid(g, g.nz)), dim3(WL_BLOCK), 0, s, g, uout, uin, x, pout, sigma, dt, cl, kfirst, klast, ws.pm, 0, g.nz, store_sigma, bc);
     hipLaunchKernelGGL(k_fin_max_enc, dim3(1), dim3(WL_BLOCK), 0, s, reinterpret_cast<const int*>(ws.pm), ws.res_f + slot_f);
     WL_LAUNCH_CHECK(); return 0;
   }

@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "wl_common.hpp"
+#include "wl_pdefer.hpp"
 
 namespace {
 
@@ -44,11 +45,13 @@ long g_resjac_min = 6L << 20;   // cells: below this the extra host read of Σr 
 #undef RJ_NS
 
 // x_out = x·dt on the cells the march does not own: the ghost shell (mom_project!'s `b.x .*= dt` scales ALL cells, src/Flow.jl:225)
-__global__ void k_scale_shell(GridX g, float* __restrict__ xout, const float* __restrict__ p, float dt) {
+// dt_prev ≠ 0: p is a scaled pressure with `./= dt_prev` pending (k_resjac<1>) — the shell takes the same two operations
+__device__ __forceinline__ float rj_rescale(float v, float dt, float dt_prev) { return dt_prev != 0.f ? wl_unscale(v, dt_prev) * dt : v * dt; }
+__global__ void k_scale_shell(GridX g, float* __restrict__ xout, const float* __restrict__ p, float dt, float dt_prev) {
   const int k = blockIdx.y;
   const long base = (long)k * g.sz;
   if (k == 0 || k == g.nz - 1) {
-    for (long m = (long)blockIdx.x * WL_BLOCK + threadIdx.x; m < g.sz; m += (long)gridDim.x * WL_BLOCK) xout[base + m] = p[base + m] * dt;
+    for (long m = (long)blockIdx.x * WL_BLOCK + threadIdx.x; m < g.sz; m += (long)gridDim.x * WL_BLOCK) xout[base + m] = rj_rescale(p[base + m], dt, dt_prev);
     return;
   }
   const long ring = 2L * g.nx + 2L * (g.ny - 2);
@@ -57,11 +60,13 @@ __global__ void k_scale_shell(GridX g, float* __restrict__ xout, const float* __
     if (q < g.nx) m = q;                                             // row 0
     else if (q < 2L * g.nx) m = (long)(g.ny - 1) * g.sy + (q - g.nx);   // row ny−1
     else { const long t = q - 2L * g.nx; const long jj = 1 + (t >> 1); m = jj * g.sy + ((t & 1) ? g.nx - 1 : 0); }   // columns 0 and nx−1
-    xout[base + m] = p[base + m] * dt;
+    xout[base + m] = rj_rescale(p[base + m], dt, dt_prev);
   }
 }
 // does the ghost shell of p hold anything but +0?  (then x_out's shell — zero since allocation, rewritten as 0/dt by the projection tails — already IS p·dt
 // and k_scale_shell can be skipped: 0.05 ms per solve at 512³, the strided columns make it slow for its size)
+// The shortcut STAYS VALID with a pending unscale: a tail that does not store p does not touch the other array's shell either, so both shells keep the +0 they
+// were found with, and (+0/dt_prev)·dt = +0 for the Δt > 0 of a time step — the shell of x_out is what the stored form would have left there.
 __global__ void k_shell_nonzero(GridX g, const float* __restrict__ p, int* __restrict__ flag) {
   const int k = blockIdx.y;
   const long base = (long)k * g.sz;
@@ -117,6 +122,9 @@ int shell_nonzero(const float* a, const GridX& g, int* dev_flag, hipStream_t s) 
   return h ? 1 : 0;
 }
 int resjac(float* xout, float* rout, const float* x, const float* u, const GridX& g, float dt, float w, const ConstL& cl, const RedWs& ws, int slot_d, int slot_f, hipStream_t s, bool shell, const float* bcU) {
+  return resjac(xout, rout, x, u, g, dt, w, cl, ws, slot_d, slot_f, s, shell, bcU, 0.f);
+}
+int resjac(float* xout, float* rout, const float* x, const float* u, const GridX& g, float dt, float w, const ConstL& cl, const RedWs& ws, int slot_d, int slot_f, hipStream_t s, bool shell, const float* bcU, float dt_prev) {
   if (xout == x) { wl_set_error("resjac: output aliases input"); return WL_EINVAL; }
   const int np = g.k1 - g.k0;
   // 16-row tiles (512 threads, four resident workgroups per CU): measured faster at every size (tools/rj_rows.sh: head 0.30 -> 0.275 ms/step at 256³,
@@ -147,11 +155,12 @@ int resjac(float* xout, float* rout, const float* x, const float* u, const GridX
   const int nch = (np + zc - 1) / zc;
   const unsigned nb = (unsigned)(8 * per * nch);
   if (nb > WL_MAXPART) { wl_set_error("resjac: too many workgroups for the reduction workspace"); return WL_EINVAL; }
-  if (shell) hipLaunchKernelGGL(k_scale_shell, dim3(8, (unsigned)g.nz), dim3(WL_BLOCK), 0, s, g, xout, x, dt);
+  if (dt_prev != 0.f && !(dt_prev > 0.f && dt > 0.f)) { wl_set_error("resjac: a pending unscale needs positive Δt"); return WL_EINVAL; }
+  if (shell) hipLaunchKernelGGL(k_scale_shell, dim3(8, (unsigned)g.nz), dim3(WL_BLOCK), 0, s, g, xout, x, dt, dt_prev);
   RjBc bc{0, {0.f, 0.f, 0.f}};
   if (bcU) { if (g.nz != g.gnz) { wl_set_error("resjac: BC! on load is for the single domain"); return WL_EINVAL; } bc.on = 1; for (int a = 0; a < 3; a++) bc.U[a] = bcU[a]; }
-  if (r16) rj16::rj_launch(nb, s, g, xout, rout, x, u, dt, w, cl, zc, ws.pa, ws.pb, ws.pm, bc);
-  else rj32::rj_launch(nb, s, g, xout, rout, x, u, dt, w, cl, zc, ws.pa, ws.pb, ws.pm, bc);
+  if (r16) rj16::rj_launch(nb, s, g, xout, rout, x, u, dt, dt_prev, w, cl, zc, ws.pa, ws.pb, ws.pm, bc);
+  else rj32::rj_launch(nb, s, g, xout, rout, x, u, dt, dt_prev, w, cl, zc, ws.pa, ws.pb, ws.pm, bc);
   hipLaunchKernelGGL(k_resjac_fin, dim3(1), dim3(WL_BLOCK), 0, s, (const double*)ws.pa, (const double*)ws.pb, (const float*)ws.pm, (int)nb, ws.res_d, ws.res_f, slot_d, slot_f);
   WL_LAUNCH_CHECK(); return 0;
 }

@@ -12,8 +12,11 @@ namespace RJ_NS {
 #ifndef RJ_WAVES
 #define RJ_WAVES 8      // waves per SIMD the register budget is sized for: 8 = two 1024-thread workgroups per CU, 64 VGPRs (experiments: 4)
 #endif
+// PEND: p holds the previous solve's SCALED pressure whose `b.x ./= dt_prev` (src/Flow.jl:229) was not stored (wl_sim, option "pdefer"): the division is applied
+// on load, then this solve's `b.x .*= dt` — fl(fl(x/dt_prev)·dt), the two roundings the stored form makes, in the same order
+template <int PEND>
 __global__ void __launch_bounds__(RJ_N, RJ_WAVES) k_resjac(GridX g, float* __restrict__ xout, float* __restrict__ rout, const float* __restrict__ p, const float* __restrict__ u,
-                                                    float dt, float w, wl::ConstL cl, int zchunk, double* __restrict__ psum, double* __restrict__ pl1, float* __restrict__ pmax, RjBc bc) {
+                                                    float dt, float dt_prev, float w, wl::ConstL cl, int zchunk, double* __restrict__ psum, double* __restrict__ pl1, float* __restrict__ pmax, RjBc bc) {
   __shared__ float sX[2][RJ_SZ];   // x' = x·dt of the plane whose residual is evaluated (even-x array, then odd-x array)
   __shared__ float sE[2][RJ_SZ];   // ϵ = r·iD of the plane that is relaxed
   const int ntx = (g.nx - 1 + RJ_CX - 1) / RJ_CX, nty = (g.ny - 2 + RJ_CY - 1) / RJ_CY;
@@ -48,6 +51,7 @@ __global__ void __launch_bounds__(RJ_N, RJ_WAVES) k_resjac(GridX g, float* __res
     auto ldp = [&](int K) -> float2 {                  // x' = x·dt of plane K (all cells of the array; 0 outside it)
       if (!(indom && plane_ok(K))) return make_float2(0.f, 0.f);
       const float2 v = rj_ld2(p, oc + (unsigned)K * sz);
+      if (PEND) return make_float2(wl_unscale(v.x, dt_prev) * dt, wl_unscale(v.y, dt_prev) * dt);
       return make_float2(v.x * dt, v.y * dt);
     };
     // bc.on: BC!(u,U) has NOT been applied to u since its producer wrote the interior (wl_sim defers it: the projection tail rewrites every boundary location anyway).
@@ -166,9 +170,10 @@ __global__ void __launch_bounds__(RJ_N, RJ_WAVES) k_resjac(GridX g, float* __res
 // launch geometry of this tile height
 inline int rj_tiles(const GridX& g) { return ((g.nx - 1 + RJ_CX - 1) / RJ_CX) * ((g.ny - 2 + RJ_CY - 1) / RJ_CY); }
 inline long rj_slots_per_xcd() { return 32L * (2048 / RJ_N); }      // resident workgroups per XCD at 64 VGPRs
-inline void rj_launch(unsigned nb, hipStream_t s, const GridX& g, float* xout, float* rout, const float* x, const float* u, float dt, float w, const wl::ConstL& cl, int zc,
+inline void rj_launch(unsigned nb, hipStream_t s, const GridX& g, float* xout, float* rout, const float* x, const float* u, float dt, float dt_prev, float w, const wl::ConstL& cl, int zc,
                       double* pa, double* pb, float* pm, const RjBc& bc) {
-  hipLaunchKernelGGL(k_resjac, dim3(nb), dim3(RJ_N), 0, s, g, xout, rout, x, u, dt, w, cl, zc, pa, pb, pm, bc);
+  if (dt_prev != 0.f) hipLaunchKernelGGL(k_resjac<1>, dim3(nb), dim3(RJ_N), 0, s, g, xout, rout, x, u, dt, dt_prev, w, cl, zc, pa, pb, pm, bc);
+  else hipLaunchKernelGGL(k_resjac<0>, dim3(nb), dim3(RJ_N), 0, s, g, xout, rout, x, u, dt, dt_prev, w, cl, zc, pa, pb, pm, bc);
 }
 }  // namespace RJ_NS
 #undef RJ_X

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include "wl_mg.hpp"
 #include "wl_body.hpp"
+#include "wl_pdefer.hpp"
 
 namespace {
 __device__ __forceinline__ bool cell_ij(const GridX& g, long m, int& i, int& j) {
@@ -464,9 +465,33 @@ struct wl_sim {
   static constexpr int CFL_SLOT = 5;   // res_f slot of CFL's maximum (not slot 0: a tail queued ahead of the solver's read must leave the head's L∞ there for the log)
   bool use_tailspec = true;  // the projection tail is queued behind the smoother before the host has read the norms, gated on the device by the break test (single GPU)
   long n_tailspec = 0, n_tailspec_armed = 0;   // projection tails that ran gated / solves the gated tail was armed for (the difference: withheld — capped, or the head redone)
-  int project(float w, hipStream_t s, bool with_cfl = false, bool defer_tail = false) {    // mom_project! :223-232 (defer_tail: inside mom_step!, the corrector follows)
+  // p = x/Δt NOT STORED between the solves of a time step (option "pdefer", wl_pdefer.hpp).  The unscaled pressure a projection tail writes has one reader inside
+  // mom_step! / wl_sim_mom_steps — the next projection's head, which multiplies it by its own Δt — so where that head is known to be the fused one on this handle
+  // the tail skips the store (4 of its 32 B/cell) and leaves the divisor here; the head divides on load (same two roundings: same bits).  Anything else that would
+  // read p from memory while the divisor is pending calls materialise_p first (the two-kernel head after a redo or a back-off, wl_sim_phase, wl_sim_field, the force
+  // read-outs, a failed step).  The predictor's tail qualifies when the corrector's head will be fused, the corrector's when another step follows in the same call
+  // (as lazydt: nobody can look in between); the last tail of a call always stores, so a call never returns with the divisor pending.
+  // Pointer parity: p and ps trade places at every head and at every STORING tail; a skipped store is a skipped swap, and materialise_p is that store and swap made
+  // late.  Handle-owned p: wl_sim_field("p") reports whichever array holds the pressure — a single step with one skipped store makes three swaps and ends on
+  // the other array, a K-step call makes 2K + 1.  Caller-owned p (p_home): the results must land in the caller's array, so the LAST step's first tail skips only
+  // if that leaves an even number of swaps to go (the solver's x is then p_home itself); in a multi-step call this gives 2(K−1) skipped stores, in a single step none.
+  // Should a redo in that last step break the parity after all, mom_step copies the pressure home (one D2D copy, mean-shift flows on caller-owned arrays only).
+  bool use_pdefer = true;
+  float p_scale_pending = 0.f;   // ≠ 0: `p` holds the solver's scaled x, the pressure is p / p_scale_pending
+  long n_pdefer = 0;             // tails that skipped the store
+  float* p_home = nullptr;       // caller-owned p
+  bool pdefer_ok() const { return use_pdefer && in_step && !sgs_model && !forcing && !d.has_body && head_fused_ok(); }   // (head_fused_ok: no slab, store_f, exitBC, periodic direction, body, back-off)
+  int materialise_p(hipStream_t s) {
+    if (p_scale_pending == 0.f) return 0;
+    const float dp = p_scale_pending; p_scale_pending = 0.f;
+    WL_TRY(wl::div_scalar_to(ps, p, dp, (size_t)G.cs, s));
+    std::swap(p, ps); mg->lv[0].x = p;
+    return 0;
+  }
+  int project(float w, hipStream_t s, bool with_cfl = false, bool defer_tail = false, bool more_follow = false) {    // mom_project! :223-232 (defer_tail: inside mom_step!, the corrector follows; more_follow: another step does)
     const float dtl = w * dt.back();
     cfl_done = false;
+    if (p_scale_pending != 0.f && !head_fused_ok()) WL_TRY(materialise_p(s));             // (the fused head was switched off since the tail ran: back-off, an option)
     WL_TRY(sync_u(s));                                                                     // div(u) reads the halo planes
     if (bc_deferred && !head_fused_ok()) WL_TRY(flush_bc(s));                              // (cannot happen: the deferral tested the same condition — kept as the invariant's guard)
     if (ps && use_fuse_p && !(comm && d.perdir_mask)) {   // (z-slabs: p's ghost planes are current — exchanged at the end of the last solve, scaled with the rest)
@@ -481,7 +506,15 @@ struct wl_sim {
       const int zm = 4, zna = split ? std::max(l0.g.k0, l0.za - zm) : 0, znb = split ? std::min(l0.g.k1, l0.zb + zm + 1) : 0;
       int tail_kind = 0;        // 1: projection + flux_out + max σ into the spare array, 2: projection in place, 3: left to the corrector's loader
       bool tail_stood = false;
+      bool tail_skips_p = false;   // the tail launched last left p = x/Δt to the next fused head (decided per launch: a gated tail that was withheld is launched again)
+      auto skip_p_now = [&]() -> bool {
+        if (!pdefer_ok()) return false;
+        if (with_cfl) return more_follow;                             // the corrector's tail: the next reader is the next step's head
+        if (!defer_tail) return false;                                // the predictor's tail: the corrector's head
+        return !p_home || more_follow || p == p_home;                 // (caller-owned p, last step of the call: see the parity rule above)
+      };
       auto launch_tail = [&](const float* go) -> int {
+        tail_skips_p = false;
         // (p is the solver's x by now, ps the array the unscaled pressure goes to: both solve() call sites swap before they call)
         if (with_cfl && use_fuse_cfl && us && !d.exitBC && !d.perdir_mask) {   // + flux_out and its maximum; projected u lands in the spare array
           tail_kind = 1;
@@ -491,14 +524,16 @@ struct wl_sim {
             if (bc_deferred && !(fr.on && wl::project_cfl_pair_path(G, l0.cl))) WL_TRY(flush_bc(s));
             fr.usub = bc_deferred ? 1 : 0;      // flux_out reads the wall-normal boundary faces of the corrector's output: U on load
             fr.go = go;
-            WL_TRY(wl::project_cfl(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, mg->ws, CFL_SLOT, s, store_f ? 1 : 0, &fr)); bc_folded = fr.on != 0;
+            tail_skips_p = wl::project_cfl_pair_path(G, l0.cl) && skip_p_now();
+            WL_TRY(wl::project_cfl(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, mg->ws, CFL_SLOT, s, store_f ? 1 : 0, &fr, tail_skips_p)); bc_folded = fr.on != 0;
           }
         } else if (split) { tail_kind = 2; WL_TRY(wl::project_unscale_split(u, mu0, p, ps, G, dtl, l0.cl, l0.clp, zna, znb, s)); }
         else if (defer_tail && tailfuse_ok()) {   // p = x/Δt now; u −= L∇x and BC! when the corrector reads u (the scaled x stays untouched in the spare pressure array until then)
           tail_kind = 3;
-          WL_TRY(wl::div_scalar_to(ps, p, dtl, (size_t)G.cs, s));
+          tail_skips_p = skip_p_now();        // (with the store skipped this tail launches nothing at all: the corrector's head takes x with the pending divisor)
+          if (!tail_skips_p) WL_TRY(wl::div_scalar_to(ps, p, dtl, (size_t)G.cs, s));
         }
-        else { tail_kind = 2; BcFold fr = fold_req(1); fr.go = go; WL_TRY(wl::project_unscale(u, mu0, p, ps, G, dtl, l0.cl, s, &fr)); bc_folded = fr.on != 0; }
+        else { tail_kind = 2; BcFold fr = fold_req(1); fr.go = go; tail_skips_p = skip_p_now(); WL_TRY(wl::project_unscale(u, mu0, p, ps, G, dtl, l0.cl, s, &fr, tail_skips_p)); bc_folded = fr.on != 0; }
         return 0;
       };
       // the forms that honour the flag: the in-place tail and the pair tail with CFL (not the z-split of a body, not the corrector-loader form)
@@ -511,7 +546,7 @@ struct wl_sim {
           // p's and the spare's ghost cells are +0 unless someone wrote them from outside (checked once after a pointer to p was handed out): no shell pass then
           if (comm) p_shell = 1;   // (a slab's ghost planes hold the neighbours' pressure: always scaled with the rest)
           if (p_shell < 0) p_shell = (wl::shell_nonzero(p, G, (int*)(mg->ws.res_f + 7), s) || wl::shell_nonzero(ps, G, (int*)(mg->ws.res_f + 7), s)) ? 1 : 0;
-          WL_TRY(wl::resjac(ps, l0.eps, p, u, G, dtl, 1.f, l0.cl, mg->ws, 1, 0, s, p_shell != 0, bc_deferred ? d.uBC : nullptr)); }
+          WL_TRY(wl::resjac(ps, l0.eps, p, u, G, dtl, 1.f, l0.cl, mg->ws, 1, 0, s, p_shell != 0, bc_deferred ? d.uBC : nullptr, p_scale_pending)); }
         if (use_headspec && !comm && itmx >= 1) {
           // solver! runs its V-cycle at least once whatever the initial norms are (src/MultiLevelPoisson.jl:113-123), so Σr is not needed before the first cycle is
           // queued: the cycle is launched behind the head at once and Σr comes back with the first iteration's norms (one host round trip per solve fewer, no idle
@@ -546,7 +581,9 @@ struct wl_sim {
         }
         }
       }
+      if (head_done) p_scale_pending = 0.f;      // the head took the pending divisor on load
       if (!head_done) {
+        WL_TRY(materialise_p(s)); // … and reads p as the unscaled pressure (after a discarded solve p is the scaled x again, untouched: the head only read it)
         WL_TRY(flush_bc(s));      // the two-kernel head reads u's boundary faces from memory
         ProfScope pr(WL_PROF_RESIDUAL, s);
         if (l0.part && mg->use_zsplit && !comm) {   // a body: coefficients from the position on the plane ranges away from it (as in smooth!)
@@ -561,7 +598,8 @@ struct wl_sim {
       if (tail_kind == 3) {   // deferred into the corrector's loader (tailfuse)
         bc_deferred = false;                  // (the corrector's loader reads this u through the projection AND BC!: nothing in memory is missing)
         proj_pending = p;
-        std::swap(p, ps); l0.x = p;
+        if (tail_skips_p) { p_scale_pending = dtl; n_pdefer++; }
+        else { std::swap(p, ps); l0.x = p; }
         n_tailfuse++;
         return 0;
       }
@@ -570,10 +608,12 @@ struct wl_sim {
         WL_TRY(wl::combine_results(comm, mg->ws, s));   // max over ranks — issued BEFORE the u exchange starts on the other stream, so that
         std::swap(u, us); cfl_done = true;              // exchange stays in flight across the Δt read-back and the next predictor's interior
       }
-      std::swap(p, ps); l0.x = p;
+      if (tail_skips_p) { p_scale_pending = dtl; n_pdefer++; }      // p stays the solver's x; no store, no swap
+      else { std::swap(p, ps); l0.x = p; }
       bc_deferred = false;      // the tails update a cell from its own value only; whatever BC! had not been applied is applied now (folded stores or bc_u)
       return bc_u(s);
     }
+    WL_TRY(materialise_p(s));      // (guard: nothing defers on a handle that takes this path)
     WL_TRY(flush_bc(s));
     WL_TRY(wl::div_scale(sigma, p, u, G, dtl, s));                                       // z=div(u); x.*=dt
     WL_TRY(mg->solve(2e-3, itmx, nullptr, nullptr, nullptr, s));
@@ -604,7 +644,11 @@ struct wl_sim {
   }
   int mom_step(hipStream_t s, bool more_follow = false) {
     const int rc = mom_step_body(s, more_follow);
-    if (rc != 0) { bc_deferred = false; dt_pending = false; }   // a failed step leaves no deferred BC! and no Δt on the device for the next call to take
+    if (rc != 0) { bc_deferred = false; dt_pending = false; (void)materialise_p(s); p_scale_pending = 0.f; return rc; }   // a failed step leaves no deferred BC!, no Δt on the device and no pending divisor for the next call to take
+    if (!more_follow && p_home && p != p_home) {      // caller-owned p that ended on the spare array (a redo inside the last step): copy it home
+      WL_HIP(hipMemcpyAsync(p_home, p, sizeof(float) * (size_t)G.cs, hipMemcpyDeviceToDevice, s));
+      ps = p; p = p_home; mg->lv[0].x = p;
+    }
     return rc;
   }
   int mom_step_body(hipStream_t s, bool more_follow) {                                   // mom_step! :156-167 (more_follow: wl_sim_mom_steps — another step comes inside the same call)
@@ -622,9 +666,9 @@ struct wl_sim {
       dt_pending = false;
     } else
     WL_TRY(predict(s));
-    WL_TRY(project(1.f, s, false, true));
+    WL_TRY(project(1.f, s, false, true, more_follow));
     WL_TRY(correct(s));
-    WL_TRY(project(0.5f, s, true));
+    WL_TRY(project(0.5f, s, true, false, more_follow));
     WL_TRY(flush_bc(s));      // (nothing is pending here: every projection ends with BC! applied — guard)
     return cfl(s, more_follow);
   }
@@ -721,6 +765,7 @@ static int sim_create_common(wl_sim** out, const wl_sim_desc* desc, wl_comm* com
   else if (desc->us && (none || all3) && rot_ok) s->us = desc->us;   // caller-owned spare: the roles of {u,u0,us} rotate (wlhip.h)
   s->ps = pcur; pcur += nc;
   s->dt.assign(1, desc->dt0);
+  if (desc->p) s->p_home = desc->p;
   if (desc->p) s->p_shell = 2;     // a caller-owned p can be written behind the library's back: its ghost shell is always scaled
   s->swap_ok = (none || all3) && rot_ok;
   // μ₀ = 1 with BC!(μ₀,0)   src/Flow.jl:144-145  (only when the handle owns μ₀; a caller-owned μ₀ is taken as is)
@@ -811,6 +856,7 @@ int wl_sim_destroy(wl_sim* s) { delete s; return 0; }
 float* wl_sim_field(wl_sim* s, const char* name) {
   const std::string n(name);
   (void)s->sync_u(0);        // the caller is about to read or write the arrays: finish an exchange that is still in flight
+  if (n == "p") (void)s->materialise_p(0);      // (a call never returns with the divisor pending: guard)
   if (n == "V" || n == "mu1" || n == "mu0") s->mask_valid = false;
   if (n == "u") return s->u; if (n == "u0") return s->u0; if (n == "f") return s->f; if (n == "p") { if (s->p_shell != 2) s->p_shell = -1; return s->p; }
   if (n == "sigma") return s->sigma; if (n == "V") return s->V; if (n == "mu0") return s->mu0; if (n == "mu1") return s->mu1;
@@ -865,6 +911,7 @@ int wl_sim_set_option(wl_sim* s, const char* name, int value) {
   if (n == "tailspec") { s->use_tailspec = value != 0; return 0; }                             // the projection tail is queued ahead of the solver's convergence read, gated by the device's break test (default 1)
   if (n == "headspec") { s->use_headspec = value != 0; return 0; }                             // the first V-cycle is queued behind the fused head before Σr is known (default 1)
   if (n == "bcdefer") { s->use_bcdefer = value != 0; return 0; }                               // mom_step!: BC! after the fused conv_diff!+BDIM! left to the projection (its head reads U on the wall-normal faces, its tail rewrites the boundary); default 1
+  if (n == "pdefer") { s->use_pdefer = value != 0; return 0; }                                 // mom_step!: a projection tail whose p = x/Δt is read next by a fused head of the same call does not store it (default 1)
   if (n == "tailfuse") { s->use_tailfuse = value != 0; return 0; }                             // mom_step!: the first projection's u −= L∇x + BC! inside the corrector's conv_diff! (default 0: no gain measured)
   if (n == "convf") { wl::conv_flux_enable(value != 0); return 0; }                            // 1: tiled conv_diff! evaluates every flux once (default), 0: k_conv_tile
   if (n == "convt") { wl::conv_tile_enable(value != 0, value > 1 ? value : 0); return 0; }   // 0 off, 1 on, >1: on with that z-chunk
@@ -891,6 +938,7 @@ int wl_sim_counter(wl_sim* s, const char* name, long* out) {
   if (n == "resjac_backoff") { *out = s->resjac_backoff ? 1 : 0; return 0; }
   if (n == "tailfuse") { *out = s->n_tailfuse; return 0; }
   if (n == "bcdefer") { *out = s->n_bcdefer; return 0; }
+  if (n == "pdefer") { *out = s->n_pdefer; return 0; }
   if (n == "tailspec") { *out = s->n_tailspec; return 0; }
   if (n == "tailspec_armed") { *out = s->n_tailspec_armed; return 0; }
   if (n == "xdefer") { *out = s->mg->last_xdefer; return 0; }
@@ -928,6 +976,7 @@ int wl_sim_set_dt_last(wl_sim* s, float dt) { WL_CHECK(s && dt > 0.f, "bad Δt")
 double wl_sim_time(const wl_sim* s) { float t = 0.f; for (size_t k = 0; k + 1 < s->dt.size(); k++) t += s->dt[k]; return (double)t; }
 int wl_sim_phase(wl_sim* s, int phase, void* st) {
   hipStream_t q = wl_stream(st);
+  WL_TRY(s->materialise_p(q));      // (guard, as in wl_sim_field)
   switch (phase) {
     case 0: WL_TRY(s->sync_u(q)); WL_HIP(hipMemcpyAsync(s->u0, s->u, sizeof(float) * (size_t)s->G.cs * s->d.D, hipMemcpyDeviceToDevice, q)); return wl::scale_u(s->u, s->G, 0.f, q);
     case 1: return s->predict(q);
@@ -1029,6 +1078,7 @@ int wl_viscous_moment_body(const float* x0, const float* u, const wl_grid* g, fl
 }
 int wl_sim_pressure_moment_body(wl_sim* s, const float* x0, const wl_body* body, double* out, void* st) {
   WL_CHECK(x0, "null x0");
+  WL_TRY(s->materialise_p(wl_stream(st)));
   BodyArg bd; WL_TRY(to_body_arg(s->d.D, body, &bd));
   return force_reduce(0, s->p, 0.f, s->G, bd, s->mg->ws, s->comm, out, wl_stream(st), x0);
 }
@@ -1048,6 +1098,7 @@ int wl_sim_measure_body(wl_sim* s, const wl_body* body, float eps, void* st) {
   return s->mg->update(q);                                                                                                          // WaterLily.jl:148
 }
 int wl_sim_pressure_force_body(wl_sim* s, const wl_body* body, double* out, void* st) {
+  WL_TRY(s->materialise_p(wl_stream(st)));
   BodyArg bd; WL_TRY(to_body_arg(s->d.D, body, &bd));
   return force_reduce(0, s->p, 0.f, s->G, bd, s->mg->ws, s->comm, out, wl_stream(st));
 }
@@ -1069,6 +1120,7 @@ static int sim_force_bodyset(int which, wl_sim* s, const float* x0, const wl_bod
   WL_CHECK(s && out, "null wl_sim / out");
   SetArg P; WL_TRY(wl::bodyset_prepare(s->d.D, set, &P));
   hipStream_t q = wl_stream(st);
+  if (which == 0) WL_TRY(s->materialise_p(q));
   if (which == 1) WL_TRY(s->sync_u(q));              // ∂u/∂z at the slab faces reads the neighbours' planes
   const float* a = which == 0 ? s->p : s->u; const float nu = which == 0 ? 0.f : s->d.nu; const GridX& G = s->G;
   return wl::force_reduce_with(G, s->mg->ws, s->comm, out, q,
