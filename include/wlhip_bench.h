@@ -32,6 +32,7 @@ int wl_placement_scores(double* out, int cap);
  * "tailspec" = projection tails that ran from inside the solver loop, ahead of the convergence read,
  * "tailspec_armed" = solves the gated tail was queued for (the difference to "tailspec": withheld — the cap was hit, or the fused head's mean shift was due),
  * "pdefer" = projection tails that did not store p = x/Δt (the next fused head divided on load): 2k − 1 for a k-step wl_sim_mom_steps call where the option is live,
+ * "tailwide" = projection tails that ran in the four-cells-per-thread form (two per step where the option is live and the shape allows it),
  * "tailfuse" = projections whose velocity update (u −= L∇x, BC!) was evaluated by the corrector's conv_diff! loader instead of a tail launch,
  * "xdefer" = what the finest level's last smooth! decided: 1 the V-cycle's x += ω·x_c↓ was applied by smoother kernel B, 0 by kernel A, −1 none yet
  * (decides which bytes bench.py books to kernels A and B) */

@@ -215,7 +215,10 @@ struct BcFold { int on; float U[3];
                 const float* go = nullptr;
                 // in (conv_diff!+BDIM! launches): Δt is read from this device location instead of the argument (wl_sim_mom_steps: the next step's predictor is queued
                 // before the host has read the CFL maximum); honoured by the flux-once tiled kernel only
-                const float* dt_dev = nullptr; };
+                const float* dt_dev = nullptr;
+                // in (projection tails): 1 = take the four-cells-per-thread form where the shape and the arrays allow it (wl_sim, option "tailwide");
+                // out: the launcher that took it sets *wide_ran = 1 (host location, optional)
+                int wide = 0; int* wide_ran = nullptr; };
 
 // ---- kernel launchers shared between the leaf C ABI and the composite handles --------------------
 namespace wl {

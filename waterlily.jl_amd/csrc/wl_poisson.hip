@@ -340,6 +340,141 @@ __global__ void __launch_bounds__(WL_BLOCK) k_project_cfl2(GridX g, float* __res
   mx = block_max(mx);
   if (threadIdx.x == 0) atomicMax(reinterpret_cast<int*>(pmax) + (blockIdx.x & (WL_ENC_SLOTS - 1)), wl_enc_f(mx));
 }
+// ---- the projection tails with FOUR x-adjacent cells per thread and 16-byte accesses (option "tailwide"; 3-D, constant coefficients, even nx, nx·ny ≡ 0 mod 4) ----
+// Same statements per cell as k_project_unscale / k_project_cfl.  A block owns WL_TW_CHUNK consecutive floats of ONE plane (about two rows at 512³), blocks in the
+// linear order of pl_pair (a chunk position keeps its XCD from plane to plane).  The plane is taken as a linear array: with nx·ny a multiple of 4 every quad
+// m = 4q of every plane and component starts on a 16-byte boundary, and so do its ±z neighbours — u, x[k∓1] and u_z[k+1] are one 16-byte load per quad, u one
+// 16-byte store per component.  The in-plane neighbours of x (±1, ±nx: nx ≡ 2 mod 4 puts the rows 8 bytes off) go through LDS: the block stages the window
+// [m0 − nx, m0 + CHUNK + nx) of x once with 16-byte loads, every x operand of the plane is then an LDS read.  u_y[j+1] is two 8-byte loads, u_x of the cell after
+// the quad one 4-byte load.  A quad may straddle a row seam (its cells are then the ghosts i = nx−1, i = 0 and their interior neighbours): every cell carries its
+// own (i,j), and only a quad of four cells that take a plain store is stored 16 bytes wide — the others go through the per-cell path of the pair kernels.
+// LDS cells of the window that lie outside the plane (before its first cell, past its last) are staged as 0: only ghost cells read them, and discard the result.
+// One quad per thread: two (2048-float chunks) measured slower, profiles/tailwide_experiments.md §5.
+#define WL_TW_CHUNK (4 * WL_BLOCK)
+__device__ __forceinline__ float4 tw_ld4(const float* __restrict__ p, long o) { return *reinterpret_cast<const float4*>(p + o); }
+__device__ __forceinline__ void tw_st4(float* __restrict__ p, long o, float4 v) { *reinterpret_cast<float4*>(p + o) = v; }
+static inline unsigned tw_nb8(const GridX& g) { const long nb = (g.sz + WL_TW_CHUNK - 1) / WL_TW_CHUNK; return (unsigned)(((nb + 7) >> 3) << 3); }
+static inline unsigned tw_grid(const GridX& g, int nplanes) { return tw_nb8(g) * (unsigned)nplanes; }
+static inline size_t tw_lds_bytes(const GridX& g) { return (size_t)(WL_TW_CHUNK + 2 * g.sy + 8) * sizeof(float); }
+// CFL = 0: the in-place tail (u_out is u, u_in unused); CFL = 1: out of place + flux_out + max σ.  SP = 0: p_out is not stored (skip_p, wl_pdefer.hpp)
+template <int CFL, int SP>
+__global__ void __launch_bounds__(WL_BLOCK) k_project_wide(GridX g, float* __restrict__ uout, const float* __restrict__ uin, const float* __restrict__ x, float* __restrict__ pout,
+                                                              float* __restrict__ sigma, float dt, wl::ConstL cl, int kfirst, int klast, float* __restrict__ pmax, int p0, int p1,
+                                                              int store_sigma, BcFold bc, unsigned nb8) {
+  if (bc.go && !(*bc.go > 0.f)) return;   // (block-uniform; the maximum's slots keep k_enc_init's −∞)
+  extern __shared__ float4 tw_sh[];
+  float* __restrict__ xs = reinterpret_cast<float*>(tw_sh);
+  const float* __restrict__ ui = CFL ? uin : uout;
+  const unsigned h = blockIdx.x, p = h / nb8;
+  const int k = p0 + (int)p;
+  const long m0 = (long)(h - p * nb8) * WL_TW_CHUNK;
+  float mx = -INFINITY;
+  if (m0 < g.sz && k < p1) {            // (block-uniform)
+    const long ko = (long)k * g.sz;
+    const int sy = (int)g.sy;
+    const long base = (m0 - sy) & ~3L;  // plane index of xs[0] (negative on the first chunk)
+    const bool zin = k >= g.k0 && k < g.k1;
+    if (zin) {                          // stage x[base .. m0 + CHUNK (+ nx)) of plane k: every LDS cell a quad of this block reads; 0 outside the plane
+      const long whi = (m0 + WL_TW_CHUNK + (CFL ? sy : 0) + 3) & ~3L;
+      for (long q = base + 4 * (long)threadIdx.x; q < whi; q += 4 * WL_BLOCK)
+        *reinterpret_cast<float4*>(xs + (q - base)) = (q >= 0 && q < g.sz) ? tw_ld4(x, ko + q) : make_float4(0.f, 0.f, 0.f, 0.f);
+      __syncthreads();
+    }
+    const float lz = wl::wl_cl_coef(g.gk + k + 1, g.gnz, cl.c[2]), lzp = wl::wl_cl_coef(g.gk + k + 2, g.gnz, cl.c[2]);
+    const bool want = CFL && k >= kfirst && k < klast;
+    const long m = m0 + 4 * (long)threadIdx.x;
+    if (m < g.sz) {
+      const long o = ko + m;
+      const int r = (int)(m - base);    // xs[r] is cell 0 of the quad
+      const float4 xq = zin ? *reinterpret_cast<const float4*>(xs + r) : tw_ld4(x, o);
+      const float X[6] = {zin ? xs[r - 1] : 0.f, xq.x, xq.y, xq.z, xq.w, (CFL && zin) ? xs[r + 4] : 0.f};
+      if (SP) tw_st4(pout, o, make_float4(wl_unscale(xq.x, dt), wl_unscale(xq.y, dt), wl_unscale(xq.z, dt), wl_unscale(xq.w, dt)));
+      const int j0 = (int)(m / g.nx), i0 = (int)(m - (long)j0 * g.nx);
+      int ii[4], jj[4]; bool in[4];
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        int i = i0 + c, j = j0;
+        if (i >= g.nx) { i -= g.nx; j++; }
+        ii[c] = i; jj[c] = j;
+        in[c] = zin && i >= 1 && i <= g.nx - 2 && j >= 1 && j <= g.ny - 2;
+      }
+      float sg[4] = {0.f, 0.f, 0.f, 0.f};
+      if (in[0] || in[1] || in[2] || in[3]) {
+        const float2 ym0 = *reinterpret_cast<const float2*>(xs + r - sy), ym1 = *reinterpret_cast<const float2*>(xs + r - sy + 2);
+        const float XYM[4] = {ym0.x, ym0.y, ym1.x, ym1.y};
+        const float4 zmq = tw_ld4(x, o - g.sz);
+        const float XZM[4] = {zmq.x, zmq.y, zmq.z, zmq.w};
+        const float4 a0q = tw_ld4(ui, o), a1q = tw_ld4(ui, g.cs + o), a2q = tw_ld4(ui, 2 * g.cs + o);
+        float A0[5] = {a0q.x, a0q.y, a0q.z, a0q.w, 0.f};
+        const float A1[4] = {a1q.x, a1q.y, a1q.z, a1q.w}, A2[4] = {a2q.x, a2q.y, a2q.z, a2q.w};
+        float XYP[4] = {0.f, 0.f, 0.f, 0.f}, XZP[4] = {0.f, 0.f, 0.f, 0.f}, A1P[4] = {0.f, 0.f, 0.f, 0.f}, A2P[4] = {0.f, 0.f, 0.f, 0.f};
+        if (CFL) {
+          const float2 yp0 = *reinterpret_cast<const float2*>(xs + r + sy), yp1 = *reinterpret_cast<const float2*>(xs + r + sy + 2);
+          XYP[0] = yp0.x; XYP[1] = yp0.y; XYP[2] = yp1.x; XYP[3] = yp1.y;
+          const float4 zpq = tw_ld4(x, o + g.sz), a2pq = tw_ld4(ui, 2 * g.cs + o + g.sz);     // (zin: plane k+1 exists)
+          XZP[0] = zpq.x; XZP[1] = zpq.y; XZP[2] = zpq.z; XZP[3] = zpq.w;
+          A2P[0] = a2pq.x; A2P[1] = a2pq.y; A2P[2] = a2pq.z; A2P[3] = a2pq.w;
+          A0[4] = ui[o + 4];                                                                    // (at the plane's end these reach into plane k+1, which exists)
+          const float2 b0 = *reinterpret_cast<const float2*>(ui + g.cs + o + sy), b1 = *reinterpret_cast<const float2*>(ui + g.cs + o + sy + 2);
+          A1P[0] = b0.x; A1P[1] = b0.y; A1P[2] = b1.x; A1P[3] = b1.y;
+        }
+        float V[4][3]; bool plain[4];
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+          const int i = ii[c], j = jj[c];
+          const float xc = X[c + 1];
+          const float lx = wl::wl_cl_coef(i + 1, g.nx, cl.c[0]), ly = wl::wl_cl_coef(j + 1, g.ny, cl.c[1]);
+          float a0 = A0[c], a0n = A0[c + 1], a1 = A1[c], a1p = A1P[c], a2 = A2[c], a2p = A2P[c];
+          if (CFL && bc.usub) {   // BC!(u_in,U) deferred: U on the wall-normal faces this stencil reads (index 1 and N−1 along the component's direction), as in k_project_cfl2
+            if (i == 1) a0 = bc.U[0];
+            if (i + 2 == g.nx) a0n = bc.U[0];
+            if (j == 1) a1 = bc.U[1];
+            if (j + 2 == g.ny) a1p = bc.U[1];
+            if (g.gk + k == 1) a2 = bc.U[2];
+            if (g.gk + k + 2 == g.gnz) a2p = bc.U[2];
+          }
+          const float uxn = a0 - lx * (xc - X[c]);
+          const float uyn = a1 - ly * (xc - XYM[c]);
+          const float uzn = a2 - lz * (xc - XZM[c]);
+          V[c][0] = uxn; V[c][1] = uyn; V[c][2] = uzn;
+          if (CFL) {
+            const float lxp = wl::wl_cl_coef(i + 2, g.nx, cl.c[0]), lyp = wl::wl_cl_coef(j + 2, g.ny, cl.c[1]);
+            const float uxp = a0n - lxp * (X[c + 2] - xc);
+            const float uyp = a1p - lyp * (XYP[c] - xc);
+            const float uzp = a2p - lzp * (XZP[c] - xc);
+            if (in[c]) { float s = 0.f; s += (fmaxf(0.f, uxp) + fmaxf(0.f, -uxn)); s += (fmaxf(0.f, uyp) + fmaxf(0.f, -uyn)); s += (fmaxf(0.f, uzp) + fmaxf(0.f, -uzn)); sg[c] = s; }
+          }
+          plain[c] = in[c] && (!bc.on || wl_bc_fold_plain(g, i, j, k));
+        }
+        if (plain[0] && plain[1] && plain[2] && plain[3]) {
+          tw_st4(uout, o, make_float4(V[0][0], V[1][0], V[2][0], V[3][0]));
+          tw_st4(uout, g.cs + o, make_float4(V[0][1], V[1][1], V[2][1], V[3][1]));
+          tw_st4(uout, 2 * g.cs + o, make_float4(V[0][2], V[1][2], V[2][2], V[3][2]));
+        } else {
+#pragma unroll
+          for (int c = 0; c < 4; c++) {
+            if (!in[c]) continue;
+            if (plain[c]) { uout[o + c] = V[c][0]; uout[g.cs + o + c] = V[c][1]; uout[2 * g.cs + o + c] = V[c][2]; }
+            else wl_bc_fold_store(uout, g, ii[c], jj[c], k, V[c], bc.U);
+          }
+        }
+        if (CFL && store_sigma) {
+#pragma unroll
+          for (int c = 0; c < 4; c++) if (in[c]) sigma[o + c] = sg[c];
+        }
+      }
+      if (want) {      // cells outside the interior: the stale Φ the reference leaves in σ's ghost cells takes part in maximum(σ)  (quirk Q1)
+#pragma unroll
+        for (int c = 0; c < 4; c++) if (!in[c]) sg[c] = sigma[o + c];
+        mx = fmaxf(mx, fmaxf(fmaxf(sg[0], sg[1]), fmaxf(sg[2], sg[3])));
+      }
+    }
+  }
+  if (CFL) {
+    mx = block_max(mx);
+    if (threadIdx.x == 0) atomicMax(reinterpret_cast<int*>(pmax) + (blockIdx.x & (WL_ENC_SLOTS - 1)), wl_enc_f(mx));
+  }
+}
 
 __global__ void k_fin_max_enc(const int* __restrict__ p, float* __restrict__ om) {
   float mx = -INFINITY;
@@ -1133,6 +1268,7 @@ int div_residual_split(float* z, float* xout, float* r, const float* x, const fl
 static int tail_pair_bits() { static const int v = wl_exp_int("WL_TAIL_PAIR", 2); return v; }     // bit 0: first tail, bit 1: second tail
 static int tail_pair() { return tail_pair_bits() & 1; }
 static int tail_lin(int bit) { static const int v = wl_exp_int("WL_TAIL_LIN", 1); return (v >> bit) & 1; }
+static bool project_wide_path(const GridX& g, const ConstL& cl, const void* a, const void* b, const void* c, const void* d = nullptr, const void* e = nullptr);
 int project_unscale(float* u, const float* L, const float* x, float* pout, const GridX& g, float dt, const ConstL& cl, hipStream_t s, const BcFold* fold) {
   return project_unscale(u, L, x, pout, g, dt, cl, s, fold, false);
 }
@@ -1142,6 +1278,13 @@ int project_unscale(float* u, const float* L, const float* x, float* pout, const
   BcFold bc{0, {0.f, 0.f, 0.f}};
   if (fold && fold->on && g.D == 3 && g.nz == g.gnz && g.nx >= 6 && g.ny >= 6 && g.nz >= 6) bc = *fold;
   bc.go = fold ? fold->go : nullptr;
+  if (fold && fold->wide && lin && project_wide_path(g, cl, u, x, skip_p ? nullptr : pout)) {   // four cells per thread, 16-byte accesses (k_project_wide)
+    if (fold->wide_ran) *fold->wide_ran = 1;
+    const dim3 grid(tw_grid(g, g.nz));
+    if (skip_p) hipLaunchKernelGGL((k_project_wide<0, 0>), grid, dim3(WL_BLOCK), tw_lds_bytes(g), s, g, u, nullptr, x, pout, nullptr, dt, cl, 0, 0, nullptr, 0, g.nz, 0, bc, tw_nb8(g));
+    else hipLaunchKernelGGL((k_project_wide<0, 1>), grid, dim3(WL_BLOCK), tw_lds_bytes(g), s, g, u, nullptr, x, pout, nullptr, dt, cl, 0, 0, nullptr, 0, g.nz, 0, bc, tw_nb8(g));
+    WL_LAUNCH_CHECK(); return 0;
+  }
   if (tail_pair() && lin && cl.on && (g.nx & 1) == 0 && g.k0 >= 1) {   // two cells per thread (k_project_unscale2): x[o−sz] of plane 0 is never read (k0 >= 1)
     if (skip_p) hipLaunchKernelGGL(k_project_unscale2<0>, dim3(pl_grid(g, g.nz)), dim3(WL_BLOCK), 0, s, g, u, x, pout, dt, cl, 0, g.nz, bc);
     else hipLaunchKernelGGL(k_project_unscale2<1>, dim3(pl_grid(g, g.nz)), dim3(WL_BLOCK), 0, s, g, u, x, pout, dt, cl, 0, g.nz, bc);
@@ -1181,6 +1324,15 @@ int decide_converged(const RedWs& ws, double r1tol, double rinftol, double ninsi
   hipLaunchKernelGGL(k_decide, dim3(1), dim3(1), 0, s, (const double*)ws.res_d, ws.res_f, r1tol, rinftol, ninside, check_head, slot_d, slot_f, out_slot);
   WL_LAUNCH_CHECK(); return 0;
 }
+// The four-cells-per-thread tails (k_project_wide) run where the pair tails do, on planes that are a whole number of quads, with every array on a 16-byte boundary
+// and a staging window that fits the LDS of a block.  A launcher that takes the form says so through BcFold::wide_ran.
+static bool project_wide_path(const GridX& g, const ConstL& cl, const void* a, const void* b, const void* c, const void* d, const void* e) {
+  if (!(g.D == 3 && cl.on && (g.nx & 1) == 0 && g.nx >= 8 && g.ny >= 4 && (g.sz & 3) == 0 && g.k0 >= 1 && g.k1 <= g.nz - 1)) return false;
+  if (tw_lds_bytes(g) > 48 * 1024 || (long)tw_nb8(g) * g.nz > 0x7fffffffL) return false;
+  const void* ptr[5] = {a, b, c, d, e};
+  for (int q = 0; q < 5; q++) if ((reinterpret_cast<uintptr_t>(ptr[q]) & 15) != 0) return false;
+  return true;
+}
 bool project_cfl_pair_path(const GridX& g, const ConstL& cl) { return (tail_pair_bits() & 2) && g.D == 3 && cl.on && (g.nx & 1) == 0 && g.k0 >= 1 && g.k1 <= g.nz - 1; }
 // projection tail + CFL's σ and max(σ) -> ws.res_f[slot_f]; u_out must not alias u_in
 int project_cfl(float* uout, const float* uin, const float* L, const float* x, float* pout, float* sigma, const GridX& g, float dt, const ConstL& cl, const RedWs& ws, int slot_f, hipStream_t s, int store_sigma, const BcFold* fold) {
@@ -1199,7 +1351,13 @@ int project_cfl(float* uout, const float* uin, const float* L, const float* x, f
   if (skip_p && !project_cfl_pair_path(g, cl)) { wl_set_error("project_cfl: the tail without the p store needs the two-cells-per-thread form"); return WL_EINVAL; }
   if (project_cfl_pair_path(g, cl)) {   // two cells per thread, linear order (k_project_cfl2)
     hipLaunchKernelGGL(k_enc_init, dim3(1), dim3(WL_ENC_SLOTS), 0, s, reinterpret_cast<int*>(ws.pm));
-    if (skip_p) hipLaunchKernelGGL(k_project_cfl2<0>, dim3(pl_grid(g, g.nz)), dim3(WL_BLOCK), 0, s, g, uout, uin, x, pout, sigma, dt, cl, kfirst, klast, ws.pm, 0, g.nz, store_sigma, bc);
+    if (fold && fold->wide && project_wide_path(g, cl, uout, uin, x, sigma, skip_p ? nullptr : pout)) {   // four cells per thread, 16-byte accesses (k_project_wide)
+      if (fold->wide_ran) *fold->wide_ran = 1;
+      const dim3 grid(tw_grid(g, g.nz));
+      if (skip_p) hipLaunchKernelGGL((k_project_wide<1, 0>), grid, dim3(WL_BLOCK), tw_lds_bytes(g), s, g, uout, uin, x, pout, sigma, dt, cl, kfirst, klast, ws.pm, 0, g.nz, store_sigma, bc, tw_nb8(g));
+      else hipLaunchKernelGGL((k_project_wide<1, 1>), grid, dim3(WL_BLOCK), tw_lds_bytes(g), s, g, uout, uin, x, pout, sigma, dt, cl, kfirst, klast, ws.pm, 0, g.nz, store_sigma, bc, tw_nb8(g));
+    }
+    else if (skip_p) hipLaunchKernelGGL(k_project_cfl2<0>, dim3(pl_grid(g, g.nz)), dim3(WL_BLOCK), 0, s, g, uout, uin, x, pout, sigma, dt, cl, kfirst, klast, ws.pm, 0, g.nz, store_sigma, bc);
     else hipLaunchKernelGGL(k_project_cfl2<1>, dim3(pl_grid(g, g.nz)), dim3(WL_BLOCK), 0, s, g, uout, uin, x, pout, sigma, dt, cl, kfirst, klast, ws.pm, 0, g.nz, store_sigma, bc);
     hipLaunchKernelGGL(k_fin_max_enc, dim3(1), dim3(WL_BLOCK), 0, s, reinterpret_cast<const int*>(ws.pm), ws.res_f + slot_f);
     WL_LAUNCH_CHECK(); return 0;

@@ -480,6 +480,10 @@ struct wl_sim {
   float p_scale_pending = 0.f;   // ≠ 0: `p` holds the solver's scaled x, the pressure is p / p_scale_pending
   long n_pdefer = 0;             // tails that skipped the store
   float* p_home = nullptr;       // caller-owned p
+  // the projection tails with four cells per thread and 16-byte accesses (option "tailwide", k_project_wide in wl_poisson.hip): the same statements per cell, the
+  // same launches; taken where the launchers find that the shape and the arrays allow it (they report it: BcFold::wide_ran), everything else runs the one- and two-cell kernels
+  bool use_tailwide = true;
+  long n_tailwide = 0;           // tails that ran in that form
   bool pdefer_ok() const { return use_pdefer && in_step && !sgs_model && !forcing && !d.has_body && head_fused_ok(); }   // (head_fused_ok: no slab, store_f, exitBC, periodic direction, body, back-off)
   int materialise_p(hipStream_t s) {
     if (p_scale_pending == 0.f) return 0;
@@ -506,6 +510,7 @@ struct wl_sim {
       const int zm = 4, zna = split ? std::max(l0.g.k0, l0.za - zm) : 0, znb = split ? std::min(l0.g.k1, l0.zb + zm + 1) : 0;
       int tail_kind = 0;        // 1: projection + flux_out + max σ into the spare array, 2: projection in place, 3: left to the corrector's loader
       bool tail_stood = false;
+      bool tail_wide = false;      // the tail launched last took the four-cells-per-thread form
       bool tail_skips_p = false;   // the tail launched last left p = x/Δt to the next fused head (decided per launch: a gated tail that was withheld is launched again)
       auto skip_p_now = [&]() -> bool {
         if (!pdefer_ok()) return false;
@@ -514,7 +519,7 @@ struct wl_sim {
         return !p_home || more_follow || p == p_home;                 // (caller-owned p, last step of the call: see the parity rule above)
       };
       auto launch_tail = [&](const float* go) -> int {
-        tail_skips_p = false;
+        tail_skips_p = false; tail_wide = false;
         // (p is the solver's x by now, ps the array the unscaled pressure goes to: both solve() call sites swap before they call)
         if (with_cfl && use_fuse_cfl && us && !d.exitBC && !d.perdir_mask) {   // + flux_out and its maximum; projected u lands in the spare array
           tail_kind = 1;
@@ -525,7 +530,8 @@ struct wl_sim {
             fr.usub = bc_deferred ? 1 : 0;      // flux_out reads the wall-normal boundary faces of the corrector's output: U on load
             fr.go = go;
             tail_skips_p = wl::project_cfl_pair_path(G, l0.cl) && skip_p_now();
-            WL_TRY(wl::project_cfl(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, mg->ws, CFL_SLOT, s, store_f ? 1 : 0, &fr, tail_skips_p)); bc_folded = fr.on != 0;
+            int ran = 0; fr.wide = use_tailwide ? 1 : 0; fr.wide_ran = &ran;
+            WL_TRY(wl::project_cfl(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, mg->ws, CFL_SLOT, s, store_f ? 1 : 0, &fr, tail_skips_p)); bc_folded = fr.on != 0; tail_wide = ran != 0;
           }
         } else if (split) { tail_kind = 2; WL_TRY(wl::project_unscale_split(u, mu0, p, ps, G, dtl, l0.cl, l0.clp, zna, znb, s)); }
         else if (defer_tail && tailfuse_ok()) {   // p = x/Δt now; u −= L∇x and BC! when the corrector reads u (the scaled x stays untouched in the spare pressure array until then)
@@ -533,7 +539,9 @@ struct wl_sim {
           tail_skips_p = skip_p_now();        // (with the store skipped this tail launches nothing at all: the corrector's head takes x with the pending divisor)
           if (!tail_skips_p) WL_TRY(wl::div_scalar_to(ps, p, dtl, (size_t)G.cs, s));
         }
-        else { tail_kind = 2; BcFold fr = fold_req(1); fr.go = go; tail_skips_p = skip_p_now(); WL_TRY(wl::project_unscale(u, mu0, p, ps, G, dtl, l0.cl, s, &fr, tail_skips_p)); bc_folded = fr.on != 0; }
+        else { tail_kind = 2; BcFold fr = fold_req(1); fr.go = go; tail_skips_p = skip_p_now();
+               int ran = 0; fr.wide = use_tailwide ? 1 : 0; fr.wide_ran = &ran;
+               WL_TRY(wl::project_unscale(u, mu0, p, ps, G, dtl, l0.cl, s, &fr, tail_skips_p)); bc_folded = fr.on != 0; tail_wide = ran != 0; }
         return 0;
       };
       // the forms that honour the flag: the in-place tail and the pair tail with CFL (not the z-split of a body, not the corrector-loader form)
@@ -608,6 +616,7 @@ struct wl_sim {
         WL_TRY(wl::combine_results(comm, mg->ws, s));   // max over ranks — issued BEFORE the u exchange starts on the other stream, so that
         std::swap(u, us); cfl_done = true;              // exchange stays in flight across the Δt read-back and the next predictor's interior
       }
+      if (tail_wide) n_tailwide++;
       if (tail_skips_p) { p_scale_pending = dtl; n_pdefer++; }      // p stays the solver's x; no store, no swap
       else { std::swap(p, ps); l0.x = p; }
       bc_deferred = false;      // the tails update a cell from its own value only; whatever BC! had not been applied is applied now (folded stores or bc_u)
@@ -912,6 +921,7 @@ int wl_sim_set_option(wl_sim* s, const char* name, int value) {
   if (n == "headspec") { s->use_headspec = value != 0; return 0; }                             // the first V-cycle is queued behind the fused head before Σr is known (default 1)
   if (n == "bcdefer") { s->use_bcdefer = value != 0; return 0; }                               // mom_step!: BC! after the fused conv_diff!+BDIM! left to the projection (its head reads U on the wall-normal faces, its tail rewrites the boundary); default 1
   if (n == "pdefer") { s->use_pdefer = value != 0; return 0; }                                 // mom_step!: a projection tail whose p = x/Δt is read next by a fused head of the same call does not store it (default 1)
+  if (n == "tailwide") { s->use_tailwide = value != 0; return 0; }                             // the projection tails with four cells per thread and 16-byte accesses where the shape allows (default 1); 0: the one- and two-cell kernels
   if (n == "tailfuse") { s->use_tailfuse = value != 0; return 0; }                             // mom_step!: the first projection's u −= L∇x + BC! inside the corrector's conv_diff! (default 0: no gain measured)
   if (n == "convf") { wl::conv_flux_enable(value != 0); return 0; }                            // 1: tiled conv_diff! evaluates every flux once (default), 0: k_conv_tile
   if (n == "convt") { wl::conv_tile_enable(value != 0, value > 1 ? value : 0); return 0; }   // 0 off, 1 on, >1: on with that z-chunk
@@ -939,6 +949,7 @@ int wl_sim_counter(wl_sim* s, const char* name, long* out) {
   if (n == "tailfuse") { *out = s->n_tailfuse; return 0; }
   if (n == "bcdefer") { *out = s->n_bcdefer; return 0; }
   if (n == "pdefer") { *out = s->n_pdefer; return 0; }
+  if (n == "tailwide") { *out = s->n_tailwide; return 0; }
   if (n == "tailspec") { *out = s->n_tailspec; return 0; }
   if (n == "tailspec_armed") { *out = s->n_tailspec_armed; return 0; }
   if (n == "xdefer") { *out = s->mg->last_xdefer; return 0; }
