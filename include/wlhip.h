@@ -217,9 +217,12 @@ int wl_sim_init_flow(wl_sim* s, void* stream);          /* BC!(u), u⁰=u, μ₀
    "bcdefer"[1] wl_sim_mom_step: BC!(u,U) after the fused conv_diff!+BDIM! is left to the projection that follows — its fused head (and the second tail's flux_out) read U
        on the wall-normal boundary faces, its tail's folded stores rewrite every boundary location — two BC! launches fewer per step; results identical on every cell.
        Only where all of that holds (tuple U, single domain, no periodic direction / exit / body, fused head and folded tails in use); wl_sim_phase applies BC! as before.
-   "tailfuse"[0] wl_sim_mom_step: the first projection's tail (u −= L∇x, BC!) is evaluated by the corrector's conv_diff! loader; the projected predictor
-       velocity is never written (whole tiles, single domain, tuple U, no periodic direction / exit / body; results identical; measured: no gain, hence off).
+   "tailfuse"[1, on grids of at least "tailfuse_min" interior cells] wl_sim_mom_step: the first projection's tail (u −= L∇x, BC!) is evaluated by the
+       corrector's conv_diff! loader; the projected predictor velocity is never written (whole tiles, single domain, tuple U, no periodic direction / exit /
+       body; results identical).  Setting it to 1 explicitly also sets the gate to 0 (the path at any eligible size); 0 switches it off.
        wl_sim_phase always keeps the tail launch.
+   "tailfuse_min"[16 Mi cells = 256³] per handle: the size gate of "tailfuse" (256³ is the smallest size at which it was measured clearly faster; below it
+       the separate tail, which can be queued ahead of the solver's convergence read, is kept).  wl_sim_counter("tailfuse_min") reads the gate in force.
    "pdefer"[1] wl_sim_mom_step / wl_sim_mom_steps: a projection tail whose p = x/Δt would be read next by the fused projection head of the same call does not
        store it; that head takes the solver's scaled x and divides on load (same roundings in the same order: identical bits; 4 B/cell less per tail).  The
        predictor's tail when the corrector's head will be fused, the corrector's when another step follows inside wl_sim_mom_steps; the last tail of a call always

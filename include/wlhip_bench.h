@@ -34,6 +34,7 @@ int wl_placement_scores(double* out, int cap);
  * "pdefer" = projection tails that did not store p = x/Δt (the next fused head divided on load): 2k − 1 for a k-step wl_sim_mom_steps call where the option is live,
  * "tailwide" = projection tails that ran in the four-cells-per-thread form (two per step where the option is live and the shape allows it),
  * "tailfuse" = projections whose velocity update (u −= L∇x, BC!) was evaluated by the corrector's conv_diff! loader instead of a tail launch,
+ * "tailfuse_min" = no count: the size gate of that path in force on this handle (interior cells; option "tailfuse_min"),
  * "xdefer" = what the finest level's last smooth! decided: 1 the V-cycle's x += ω·x_c↓ was applied by smoother kernel B, 0 by kernel A, −1 none yet
  * (decides which bytes bench.py books to kernels A and B) */
 int wl_sim_counter(wl_sim* s, const char* name, long* out);

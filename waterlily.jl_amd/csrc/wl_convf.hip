@@ -42,6 +42,7 @@ namespace {
 #define CF_FBUF (CF_FY + CF_FX)                 // one flux buffer (3312 floats)
 #define CF_NGEN (3 * CF_CX + 3 * CF_CY)         // 240 generic faces per plane
 #define CF_LDS (CF_NSLOT * CF_SLOT + 2 * CF_FBUF)   // 18864 floats = 75,456 B: two workgroups per CU
+#define CF_GENC 5                                   // PROJ: the generic face's five per-thread offsets live in LDS (CF_GENC × 256 words = 5,120 B; 80,576 B in all, still two workgroups per CU)
 
 struct __attribute__((aligned(4))) F2v { float x, y; };   // 8-byte global access that is only 4-byte aligned (tiles start at an odd cell)
 __device__ __forceinline__ float2 cf_ldg2(const float* __restrict__ p, unsigned o) { const F2v t = *reinterpret_cast<const F2v*>(p + o); return make_float2(t.x, t.y); }
@@ -51,6 +52,10 @@ __device__ __forceinline__ float cf_sel(const float2& v, int e) { return e ? v.y
 // value of the next lane (lane 63: unchanged)
 __device__ __forceinline__ float cf_next_lane(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
+}
+// value of the previous lane (lane 0: unchanged)
+__device__ __forceinline__ float cf_prev_lane(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
 }
 
 // see wl_convt.hip: a pair (X, X+1) of row Y whose elements may lie outside the array
@@ -93,7 +98,7 @@ int g_convf_on = 1;
 // velocity is never written (−24 B/cell of the step's traffic and one launch).  FULL tiles, single domain, no periodic direction / exit / body.
 template <int SCH, int FULL, int U0ADV, int MODE, int PROJ>
 __global__ void __launch_bounds__(CF_N, 4) k_conv_flux(GridX g, const float* __restrict__ u, float nu, int ka, int kb, int zchunk, BdimArgs bd) {
-  __shared__ float lds[CF_LDS];
+  __shared__ float lds[CF_LDS + (PROJ ? CF_GENC * 256 : 0)];
   const int ntx = (g.nx - 2 + CF_CX - 1) / CF_CX, nty = (g.ny - 2 + CF_CY - 1) / CF_CY;
   const int ntiles = ntx * nty;
   // XCD-aware map: hardware block h is dealt to XCD h%8; XCD q walks a contiguous range of tiles (a band of rows), chunk after chunk
@@ -132,6 +137,10 @@ __global__ void __launch_bounds__(CF_N, 4) k_conv_flux(GridX g, const float* __r
   const int gU0 = gb * CF_P + gF;                            // u_b[F]
   const int gUm = gU0 - (ga == 0 ? 1 : CF_W);                // u_b[F−δa] for a = x, y (a = z: the previous plane's u_b[F], carried in gprev)
   for (int i = tid; i < CF_LDS; i += CF_N) lds[i] = 0.f;
+  // PROJ: the loader's operands take the registers these five offsets would hold across the loop (they were the values the compiler spilled, and a spill
+  // reload waits for every vector-memory operation in flight): the generic face reads them back from LDS, which the vector-memory counter does not see
+  int* const genc = reinterpret_cast<int*>(lds + CF_LDS) + (tid & 255);
+  if (PROJ && gen) { genc[0] = gf; genc[256] = gsb; genc[512] = gU0; genc[768] = gUm; genc[1024] = gout; }
   __syncthreads();
 
   struct Stage { float2 c[3]; float2 h; };
@@ -173,6 +182,22 @@ __global__ void __launch_bounds__(CF_N, 4) k_conv_flux(GridX g, const float* __r
     for (int e = 0; e < 2; e++) { X.xh[e] = px[ko + ho[e]]; X.xn[e] = px[ko + ho[e] - hnb]; }
     return X;
   };
+  // The main loop's form of load_x: of the pair's x operands it loads only those no register of this wave holds — x[k−1] is the x[k] of the plane before
+  // (carried in xkp: the planes on which the z clamp makes the two differ are the planes on which the z component is U, where the operand is not used),
+  // x[i−1] is the previous lane's xc.y except for the first pair of a row.  (Carrying x[k−1] of the z-normal halo elements too costs two more resident
+  // registers than it saves in flight: 17 spilled registers against 13, profiles/tailfuse_experiments.md.)
+  struct XLean { float2 xc, xy; float xm; float xh[2], xn[2]; };
+  float2 xkp = make_float2(0.f, 0.f);      // x at the pair on the plane projected last
+  auto load_x_lean = [&](int kk) -> XLean {
+    const int kc = kk < 1 ? 1 : (kk > g.nz - 2 ? g.nz - 2 : kk);
+    const unsigned ko = (unsigned)kc * sz;
+    XLean X;
+    X.xc = cf_ldg2(px, ko + pc.off); X.xy = cf_ldg2(px, ko + pc.off - sy);
+    X.xm = 0.f; if (lx == 0) X.xm = px[ko + pc.off - 1u];
+#pragma unroll
+    for (int e = 0; e < 2; e++) { X.xh[e] = px[ko + ho[e]]; X.xn[e] = px[ko + ho[e] - hnb]; }
+    return X;
+  };
   const bool dxc0 = (x == 1), dyc = (y == 1);      // the pair's first cell lies on the lower x wall face / the row on the lower y wall face
   auto project = [&](Stage& st, const XStage& X, int kk) {
     const bool zd = kk <= 1 || kk >= g.nz - 1;     // the z component is U on these planes
@@ -186,6 +211,17 @@ __global__ void __launch_bounds__(CF_N, 4) k_conv_flux(GridX g, const float* __r
     const float h0 = st.h.x - hc * (X.xh[0] - X.xn[0]), h1 = st.h.y - hc * (X.xh[1] - X.xn[1]);
     const bool hz = hcmp == 2 && zd;
     st.h = make_float2((hd[0] || hz) ? hU : h0, (hd[1] || hz) ? hU : h1);
+  };
+  // (all lanes of the wave are active where this is called: the lane move reads the neighbour's register)
+  auto project_lean = [&](Stage& st, const XLean& L, int kk) {
+    XStage X;
+    X.xc = L.xc; X.xy = L.xy; X.xk = xkp;
+    const float pm = cf_prev_lane(L.xc.y);
+    X.xm = lx == 0 ? L.xm : pm;
+#pragma unroll
+    for (int e = 0; e < 2; e++) { X.xh[e] = L.xh[e]; X.xn[e] = L.xn[e]; }
+    project(st, X, kk);
+    xkp = L.xc;
   };
   auto slot_of = [&](int kk) -> float* { return lds + ((unsigned)(kk + 3) % 3u) * CF_SLOT; };
   auto write_plane = [&](int kk, const Stage& st) {
@@ -220,7 +256,7 @@ __global__ void __launch_bounds__(CF_N, 4) k_conv_flux(GridX g, const float* __r
       }
     }
   };
-  Stage S; XStage XS;
+  Stage S;
   // ---- prologue: planes ks−1, ks, ks+1 → LDS; plane ks−2 only at the own cells; plane ks+2 in flight.  Priming = the z-face fluxes of the first plane's lower faces
   {
     float2 m2[3];
@@ -234,9 +270,9 @@ __global__ void __launch_bounds__(CF_N, 4) k_conv_flux(GridX g, const float* __r
     if (PROJ) {
       const XStage x0s = load_x(ks - 1), x1s = load_x(ks), x2s = load_x(ks + 1);
       project(s0, x0s, ks - 1); project(s1, x1s, ks); project(s2, x2s, ks + 1);
+      xkp = x2s.xc;
     }
     S = load_plane(ks + 2);
-    if (PROJ) XS = load_x(ks + 2);
     write_plane(ks - 1, s0); write_plane(ks, s1); write_plane(ks + 1, s2);
     float2 C1[3], Zp1[3], Zp2[3];
 #pragma unroll
@@ -279,12 +315,17 @@ __global__ void __launch_bounds__(CF_N, 4) k_conv_flux(GridX g, const float* __r
     constexpr int WALLS = decltype(wtag)::value;
     for (int k = ks; k < ke; k++) {
       // ---- stage: plane k+2 (loaded during the previous iteration) → LDS; its centres are this plane's f[I+2δz]; issue plane k+3
-      if (PROJ) project(S, XS, k + 2);
+      // PROJ: only the x operands of plane k+2 are requested here; the plane is projected and staged behind the x/y fluxes (below), so the operands are in
+      // flight across arithmetic that does not need them instead of being held — as requests or as spills — across the barrier and the stores
       float2 Zp2[3];
+      XLean XL;
+      if (PROJ) XL = load_x_lean(k + 2);
+      else {
 #pragma unroll
-      for (int cc = 0; cc < 3; cc++) Zp2[cc] = FULL ? S.c[cc] : cf_pair_fix(S.c[cc], pc.mode);
-      write_plane(k + 2, S);
-      S = load_plane(k + 3);
+        for (int cc = 0; cc < 3; cc++) Zp2[cc] = FULL ? S.c[cc] : cf_pair_fix(S.c[cc], pc.mode);
+        write_plane(k + 2, S);
+        S = load_plane(k + 3);
+      }
       const unsigned ko = (unsigned)k * sz;
       float2 u0v[3];
       if (k > ks) store_plane(wtag, k - 1);
@@ -338,11 +379,19 @@ __global__ void __launch_bounds__(CF_N, 4) k_conv_flux(GridX g, const float* __r
       }
       // ---- the generic face (tile's upper x / y edge): waves 0..3
       if (gen) {
-        const float fa = S0[gf - 2 * gsb], fb = S0[gf - gsb], fc = S0[gf], fd = S0[gf + gsb];
-        const float ub0 = S0[gU0], ubm = S0[gUm];
+        const int qf = PROJ ? genc[0] : gf, qsb = PROJ ? genc[256] : gsb, qU0 = PROJ ? genc[512] : gU0, qUm = PROJ ? genc[768] : gUm, qout = PROJ ? genc[1024] : gout;
+        const float fa = S0[qf - 2 * qsb], fb = S0[qf - qsb], fc = S0[qf], fd = S0[qf + qsb];
+        const float ub0 = S0[qU0], ubm = S0[qUm];
         const float U = (ub0 + (ga == 2 ? gprev : ubm)) / 2;
         gprev = ub0;
-        FB[gout] = cf_flux<SCH, WALLS>(U, fa, fb, fc, fd, false, gwu, nu);
+        FB[qout] = cf_flux<SCH, WALLS>(U, fa, fb, fc, fd, false, gwu, nu);
+      }
+      if (PROJ) {   // plane k+2 → LDS now: its ring slot was last read before the previous barrier and is first read after this iteration's
+        project_lean(S, XL, k + 2);
+#pragma unroll
+        for (int cc = 0; cc < 3; cc++) Zp2[cc] = S.c[cc];
+        write_plane(k + 2, S);
+        S = load_plane(k + 3);
       }
       // ---- b = z: upper face k+1 (it lies on a z wall on two planes of the whole domain: block-uniform branch, the common side carries no wall forms).
       // (Evaluating it after the barrier instead, behind the reads of the neighbours' fluxes, costs registers: +8 % on the kernel, profiles/r03_experiments.md §12.)
@@ -351,13 +400,12 @@ __global__ void __launch_bounds__(CF_N, 4) k_conv_flux(GridX g, const float* __r
       const bool zwall = (Kg + 1 == 1 || Kg + 1 == g.gnz - 1);
       if (zwall) zfaces(std::integral_constant<int, 1>{}, k, Zm1, C1, Zp1, Zp2, Pp, Pz);
       else zfaces(std::integral_constant<int, 0>{}, k, Zm1, C1, Zp1, Zp2, Pp, Pz);
-      // u⁰ (used after the barrier) and, with PROJ, the pressure values of plane k+3 are requested here, behind the flux arithmetic: their registers are
+      // u⁰ (used after the barrier) is requested here, behind the flux arithmetic: its registers are
       // not live across it (8 -> 2 spilled registers in the corrector, conv_diff! 2.21 -> 2.12 ms per step) and the barrier wait covers most of their latency
       if (!U0ADV) {
 #pragma unroll
         for (int a = 0; a < 3; a++) { u0v[a] = cf_ldg2(bd.u0, (unsigned)a * cs + ko + pc.off); if (!FULL) u0v[a] = cf_pair_fix(u0v[a], pc.mode); }
       }
-      if (PROJ) XS = load_x(k + 3);
       __syncthreads();     // fluxes of this plane and plane k+2 are visible; nobody still reads the ring slot / flux buffer the next iteration overwrites
       float2 PuA[3]; float PxE[3];
 #pragma unroll

@@ -323,14 +323,19 @@ struct wl_sim {
   // corrector — so inside mom_step! the tail's u −= L∇x and the BC! after it are evaluated by that kernel's loader and the field is never written back
   // (−24 B/cell, one launch); p = x/Δt keeps its own small launch.  Only where the loader's closed form is the whole story (fold_ok: single domain, tuple U,
   // no periodic direction, no convective exit) and the corrector is the fused NoBody launch on whole tiles.
-  // OPT-IN (option "tailfuse"): bit-identical, but at 512³ the loader's extra loads cost the corrector what the tail launch took (corrector 1.19 -> 1.83 ms
-  // + 0.22 ms for p against 0.88 ms for the tail: the kernel sits at the 128-register budget of its two workgroups per CU, the x operands spill, and a
-  // spill reload's in-order vmcnt wait drains the plane prefetch) — profiles/r03_experiments.md §13.
-  bool use_tailfuse = false;
+  // ON BY DEFAULT on grids of at least `tailfuse_min` interior cells (option "tailfuse", bit-identical): since "pdefer" the predictor's tail launches nothing at
+  // all in this form, and with the lean loader (wl_convf.hip: x[k−1] carried from the plane before, x[i−1] from the neighbouring lane, the operands requested
+  // at the top of the plane and used behind the x/y fluxes, no spill reload in the loop) the corrector pays 0.19 ms at 512³ for the 0.76 ms tail it replaces
+  // (profiles/tailfuse_experiments.md).  Below the gate the separate tail is kept: it can be queued ahead of the solver's convergence read ("tailspec"), which
+  // the loader form cannot, and the counters of that speculation are what the small-grid tests pin.
+  // An explicit tailfuse = 1 lowers the gate to 0 (the path at any whole-tile size); "tailfuse_min" sets the gate itself.
+  static constexpr long TAILFUSE_MIN_DEFAULT = 16L << 20;      // interior cells = 256³: the smallest of 128³ / 256³ / 512³ at which every fused run beat every unfused one (−3.8 %; at 128³ −1 % in the mean, ranges touching)
+  bool use_tailfuse = true;
+  long tailfuse_min = TAILFUSE_MIN_DEFAULT;
   const float* proj_pending = nullptr;
   bool tailfuse_ok() const {
     return use_tailfuse && fold_ok(3) && us && !d.has_body && !forcing && !sgs_model && !store_f && !use_convz && !u_pending && mg->lv[0].cl.on && !mg->lv[0].part &&
-           wl::conv_proj_ok(G, d.perdir_mask);
+           (long)(G.nx - 2) * (G.ny - 2) * (G.gnz - 2) >= tailfuse_min && wl::conv_proj_ok(G, d.perdir_mask);
   }
   bool use_convz = false;    // z-marching conv_diff! (each flux once): bit-identical but measured 6 % SLOWER than the gather kernel at 512³ (opt-in)
   int conv_only(const float* uadv, hipStream_t s) {     // conv_diff!(f,uadv,σ) without BDIM!
@@ -922,7 +927,8 @@ int wl_sim_set_option(wl_sim* s, const char* name, int value) {
   if (n == "bcdefer") { s->use_bcdefer = value != 0; return 0; }                               // mom_step!: BC! after the fused conv_diff!+BDIM! left to the projection (its head reads U on the wall-normal faces, its tail rewrites the boundary); default 1
   if (n == "pdefer") { s->use_pdefer = value != 0; return 0; }                                 // mom_step!: a projection tail whose p = x/Δt is read next by a fused head of the same call does not store it (default 1)
   if (n == "tailwide") { s->use_tailwide = value != 0; return 0; }                             // the projection tails with four cells per thread and 16-byte accesses where the shape allows (default 1); 0: the one- and two-cell kernels
-  if (n == "tailfuse") { s->use_tailfuse = value != 0; return 0; }                             // mom_step!: the first projection's u −= L∇x + BC! inside the corrector's conv_diff! (default 0: no gain measured)
+  if (n == "tailfuse") { s->use_tailfuse = value != 0; if (value != 0) s->tailfuse_min = 0; return 0; }   // mom_step!: the first projection's u −= L∇x + BC! inside the corrector's conv_diff! (default 1 on grids of at least "tailfuse_min" cells; an explicit 1 also drops that gate)
+  if (n == "tailfuse_min") { if (value < 0) { wl_set_error("tailfuse_min: interior cells, >= 0"); return WL_EINVAL; } s->tailfuse_min = value; return 0; }   // interior-cells gate of "tailfuse" (default 16 Mi = 256³; tests: 0 or a small whole-tile shape)
   if (n == "convf") { wl::conv_flux_enable(value != 0); return 0; }                            // 1: tiled conv_diff! evaluates every flux once (default), 0: k_conv_tile
   if (n == "convt") { wl::conv_tile_enable(value != 0, value > 1 ? value : 0); return 0; }   // 0 off, 1 on, >1: on with that z-chunk
   if (n == "pair") { wl::gsrb_pair_enable(value); return 0; }
@@ -947,6 +953,7 @@ int wl_sim_counter(wl_sim* s, const char* name, long* out) {
   if (n == "resjac_redo") { *out = s->n_resjac_redo; return 0; }
   if (n == "resjac_backoff") { *out = s->resjac_backoff ? 1 : 0; return 0; }
   if (n == "tailfuse") { *out = s->n_tailfuse; return 0; }
+  if (n == "tailfuse_min") { *out = s->tailfuse_min; return 0; }      // (the gate in force, not a count: the per-handle options have no other read-out)
   if (n == "bcdefer") { *out = s->n_bcdefer; return 0; }
   if (n == "pdefer") { *out = s->n_pdefer; return 0; }
   if (n == "tailwide") { *out = s->n_tailwide; return 0; }
