@@ -272,27 +272,40 @@ struct wl_sim {
   int sgs_model = 0;         // 0 off, 1 Smagorinsky–Lilly
   float sgs_Cs = 0.f, sgs_Delta = 1.f;
   int sgs_udf(const float* uadv, hipStream_t s) { return sgs_model ? wl::sgs(f, sigma, uadv, G, sgs_Cs, sgs_Delta, s) : 0; }   // udf!(a,sgs!,uadv,t)
+  bool fused_nobody_conv() const { return us && !d.has_body && !forcing && !sgs_model; }   // predict/correct run conv_diff!+BDIM! as one launch (the NoBody form; `us`: the corrector writes out of place)
   std::vector<float> dt;
   bool own_mg = true;        // false: the multigrid handle belongs to the caller (wl_sim_create_on)
-  ~wl_sim() { if (u_pending && comm && comm->cs) (void)hipStreamSynchronize(comm->cs); if (own_mg) delete mg; if (own) (void)hipFree(own); if (exit_sc) (void)hipFree(exit_sc); if (farmask) (void)hipFree(farmask); if (mnear) (void)hipFree(mnear); if (mneedf) (void)hipFree(mneedf); if (mm0var) (void)hipFree(mm0var); }
+  // WHAT MEMORY DOES NOT HOLD YET (DESIGN.md §4.3b has the same table).  Each field: who sets it -> who consumes it; what makes memory current without it.
+  struct Deferred {
+    bool u_pending = false;          // bc_u (slabs, "overlap"): an exchange of the array that is now u or u⁰ is in flight -> the first reader of the halo planes; sync_u
+    bool bc_deferred = false;        // bc_u_or_defer: BC!(u) after the fused conv launch is not applied -> the fused head / the pair tail put U on load, every tail rewrites the boundary; flush_bc
+    bool bc_folded = false;          // a producer with folded stores (wl_bcfold.hpp) wrote every boundary location -> the next bc_u, which then launches nothing; nothing to settle
+    const float* proj_pending = nullptr;   // the tail left to the corrector's loader: u still lacks −L∇x of this x -> conv_fused, inside the same step (it fails the step otherwise); never outlives mom_step
+    float p_scale_pending = 0.f;     // a tail that skipped its store ("pdefer"): ≠ 0, p holds the solver's scaled x, the pressure is p / p_scale_pending -> the next fused head divides on load; materialise_p
+    bool dt_pending = false;         // cfl(more_follow): Δt of the next step is on the device only -> the next mom_step of the same call reads it back behind its predictor; never outlives wl_sim_mom_steps
+    bool cfl_done = false;           // the pair tail: max σ is already in CFL_SLOT -> cfl(), which then launches nothing; nothing to settle
+  } df;
+  // makes memory current for a reader outside the step (fields handed out, force read-outs, wl_sim_phase, a failed step).  Between calls nothing is pending but, on
+  // slabs, the exchange — "a call never returns with the divisor pending", every projection ends with BC! applied — so this launches nothing there.
+  int settle(hipStream_t s) { WL_TRY(sync_u(s)); WL_TRY(materialise_p(s)); return flush_bc(s); }
+  ~wl_sim() { if (df.u_pending && comm && comm->cs) (void)hipStreamSynchronize(comm->cs); if (own_mg) delete mg; if (own) (void)hipFree(own); if (exit_sc) (void)hipFree(exit_sc); if (farmask) (void)hipFree(farmask); if (mnear) (void)hipFree(mnear); if (mneedf) (void)hipFree(mneedf); if (mm0var) (void)hipFree(mm0var); }
 
   // BC!(u) on the physical faces this rank holds, then the z-halo planes (depth 2: QUICK reads f[I-2δ], src/Flow.jl:8)
   // On slabs the exchange runs on the communicator's own stream; the compute stream waits for it (sync_u) only where the halo
   // planes are first read, so the interior planes of the next conv_diff! overlap with the transfer.
   bool use_overlap = true;
-  bool u_pending = false;    // an exchange of the array that is now `u` or `u0` is in flight
-  int sync_u(hipStream_t s) { if (u_pending) { u_pending = false; return wl::halo_async_wait(comm, s); } return 0; }
+  int sync_u(hipStream_t s) { if (df.u_pending) { df.u_pending = false; return wl::halo_async_wait(comm, s); } return 0; }
   // BC!(u,U) folded into the stores of the kernel that produced u (wl_bcfold.hpp): single domain, tuple U, no exit, no periodic direction
   // measured at 512³: projection tails −0.04 ms/step (kept), tiled conv_diff! +0.2…0.4 ms/step — the ghost writes are sector-granular
   // wherever they happen, and inside the tiled kernel they sit on the wall tiles' critical path (off; `bcfold` = 3 turns it on)
-  int use_bcfold = 1; bool bc_folded = false;    // bit 0: projection tails, bit 1: tiled conv_diff!+BDIM!
+  int use_bcfold = 1;         // bit 0: projection tails, bit 1: tiled conv_diff!+BDIM!
   bool fold_ok(int bit) const { return (use_bcfold & bit) && d.D == 3 && !comm && !d.exitBC && !d.perdir_mask && G.nz == G.gnz && G.nx >= 6 && G.ny >= 6 && G.nz >= 6; }
   BcFold fold_req(int bit) const { BcFold f{fold_ok(bit) ? 1 : 0, {d.uBC[0], d.uBC[1], d.uBC[2]}}; return f; }
   int bc_u(hipStream_t s) {
     WL_TRY(sync_u(s));
-    if (bc_folded) { bc_folded = false; return 0; }      // the producer already wrote every boundary location
+    if (df.bc_folded) { df.bc_folded = false; return 0; }      // the producer already wrote every boundary location
     WL_TRY(wl::bc_vec(u, G, d.uBC, d.exitBC, d.perdir_mask, s));
-    if (comm && use_overlap) { WL_TRY(wl::halo_async_begin(comm, u, G, d.D, 2, s)); u_pending = true; return 0; }
+    if (comm && use_overlap) { WL_TRY(wl::halo_async_begin(comm, u, G, d.D, 2, s)); df.u_pending = true; return 0; }
     return wl::halo(comm, u, G, d.D, 2, s);
   }
   // fused conv_diff!+BDIM! (NoBody): interior planes first when the advecting field's halo is still in flight
@@ -302,7 +315,7 @@ struct wl_sim {
   int conv_fused(const float* uadv, float* uout, float pre, float post, hipStream_t s, bool want_q1 = true, const float* dt_dev = nullptr) {
     const wl::ConstL& cl = mg->lv[0].cl;
     float* f = store_f ? this->f : nullptr;
-    if (u_pending && G.D == 3 && G.k1 - G.k0 > 4) {
+    if (df.u_pending && G.D == 3 && G.k1 - G.k0 > 4) {
       if (dt_dev) { wl_set_error("conv_fused: Δt on the device is for the single domain"); return WL_EINVAL; }
       WL_TRY(wl::conv_diff_bdim(f, uadv, sigma, u0, mu0, uout, G, d.nu, d.perdir_mask, d.scheme, dt.back(), pre, post, cl, s, G.k0 + 2, G.k1 - 2, false));
       WL_TRY(sync_u(s));
@@ -311,12 +324,12 @@ struct wl_sim {
     }
     WL_TRY(sync_u(s));
     BcFold fr = fold_req(2);
-    fr.proj_x = proj_pending;
+    fr.proj_x = df.proj_pending;
     fr.dt_dev = dt_dev;
     WL_TRY(wl::conv_diff_bdim(f, uadv, sigma, u0, mu0, uout, G, d.nu, d.perdir_mask, d.scheme, dt.back(), pre, post, cl, s, -(1 << 30), 1 << 30, want_q1, &fr));
-    if (proj_pending && !fr.proj_done) { wl_set_error("mom_step!: the corrector did not take the deferred projection"); return WL_EINVAL; }
-    proj_pending = nullptr;
-    bc_folded = fr.on != 0;
+    if (df.proj_pending && !fr.proj_done) { wl_set_error("mom_step!: the corrector did not take the deferred projection"); return WL_EINVAL; }
+    df.proj_pending = nullptr;
+    df.bc_folded = fr.on != 0;
     return 0;
   }
   // mom_project!'s first tail deferred into the corrector's conv_diff! (wl_convf.hip, PROJ): the projected predictor velocity has exactly one reader — the
@@ -332,9 +345,8 @@ struct wl_sim {
   static constexpr long TAILFUSE_MIN_DEFAULT = 16L << 20;      // interior cells = 256³: the smallest of 128³ / 256³ / 512³ at which every fused run beat every unfused one (−3.8 %; at 128³ −1 % in the mean, ranges touching)
   bool use_tailfuse = true;
   long tailfuse_min = TAILFUSE_MIN_DEFAULT;
-  const float* proj_pending = nullptr;
   bool tailfuse_ok() const {
-    return use_tailfuse && fold_ok(3) && us && !d.has_body && !forcing && !sgs_model && !store_f && !use_convz && !u_pending && mg->lv[0].cl.on && !mg->lv[0].part &&
+    return use_tailfuse && fold_ok(3) && fused_nobody_conv() && !store_f && !use_convz && !df.u_pending && mg->lv[0].cl.on && !mg->lv[0].part &&
            (long)(G.nx - 2) * (G.ny - 2) * (G.gnz - 2) >= tailfuse_min && wl::conv_proj_ok(G, d.perdir_mask);
   }
   bool use_convz = false;    // z-marching conv_diff! (each flux once): bit-identical but measured 6 % SLOWER than the gather kernel at 512³ (opt-in)
@@ -382,30 +394,33 @@ struct wl_sim {
     return wl::bdim(u, u0, f, nullptr, mu0, nullptr, G, dt.back(), pre, post, s);
   }
   int exit_bc(hipStream_t s);
+  static int exit_bc_single(const GridX& G, float* u, const float* u0, double* sc, float dt, hipStream_t s);   // (also behind wl_exit_bc)
   int copy_exit_face(float* dst, const float* src, hipStream_t s);
-  // BC!(u,U) after the fused conv_diff!+BDIM! DEFERRED inside mom_step! (option "bcdefer"): between that launch and the projection's tail — which rewrites
-  // every boundary location of u through its folded stores — the only reader of boundary locations is the projection head's ∇·u (and the second tail's
-  // flux_out), and only where a component is normal to the face, where BC! writes the constant U: the fused head and the pair tail substitute U on load
-  // (wl_resjac_body.inc, k_project_cfl2) and the two k_bc_vec launches per step (2 × 0.07 ms at 512³: strided x faces) disappear.  Every other path that
-  // would read u first (two-kernel head after a redo, unfused tails, wl_sim_phase, fields handed out) applies BC! before it does.
-  bool use_bcdefer = true, in_step = false, bc_deferred = false;
+  // BC!(u,U) after the fused conv_diff!+BDIM! DEFERRED inside mom_step! (option "bcdefer", df.bc_deferred): until the projection's tail rewrites every boundary
+  // location through its folded stores, boundary locations are read only where a component is normal to the face, where BC! writes the constant U — the fused
+  // head and the pair tail substitute U on load (wl_resjac_body.inc, k_project_cfl2) and the two k_bc_vec launches per step (2 × 0.07 ms at 512³: strided x
+  // faces) disappear.  Every other reader calls flush_bc first.
+  bool use_bcdefer = true, in_step = false;
   long n_bcdefer = 0;
-  bool head_fused_ok() const {      // the projection will start with the fused head (wl_resjac.hip) — the condition project() tests
+  bool head_fused_path() const {    // project() starts with the fused head (wl_resjac.hip): exactly what it tests before it launches wl::resjac
     const wl_mg::Level& l0 = mg->lv[0];
-    return ps && use_fuse_p && use_resjac && !resjac_backoff && (!resjac_force_redo || redo_unannounced) && !d.exitBC && !store_f && !d.perdir_mask && !l0.part && mg->defer_shift && mg->lv.size() > 1 &&
-           wl::resjac_ok(G, l0.cl) && !comm;
+    return ps && use_fuse_p && use_resjac && !resjac_backoff && !d.exitBC && !store_f && !d.perdir_mask && !l0.part && mg->defer_shift && mg->lv.size() > 1 && wl::resjac_ok(G, l0.cl) &&
+           (!comm || (l0.dist && mg->x_halo_depth >= 2));   // (exitBC: the convective exit leaves a net flux imbalance to the solver's tolerance — the shift is usually due; z-slab: p's ghost planes are current two deep)
   }
+  // … and a deferral (bcdefer, pdefer) may count on it.  !comm: the path allows distributed levels, the deferrals are built for the single domain; an announced
+  // forced redo (resjac = 2) is known to end on the two-kernel head, an unannounced one (3) is not — as a real shift is not
+  bool head_fused_ok() const { return head_fused_path() && !comm && (!resjac_force_redo || redo_unannounced); }
   bool bcdefer_ok(bool second) const {
-    if (!(use_bcdefer && in_step && !bc_folded && fold_ok(1) && head_fused_ok())) return false;
+    if (!(use_bcdefer && in_step && !df.bc_folded && fold_ok(1) && head_fused_ok())) return false;
     return !second || (use_fuse_cfl && us && wl::project_cfl_pair_path(G, mg->lv[0].cl));
   }
   int bc_u_or_defer(bool second, hipStream_t s) {
-    if (bcdefer_ok(second)) { bc_deferred = true; n_bcdefer++; return 0; }
+    if (bcdefer_ok(second)) { df.bc_deferred = true; n_bcdefer++; return 0; }
     return bc_u(s);
   }
   int flush_bc(hipStream_t s) {       // apply a deferred BC! now (somebody is about to read u's boundary locations from memory)
-    if (!bc_deferred) return 0;
-    bc_deferred = false;
+    if (!df.bc_deferred) return 0;
+    df.bc_deferred = false;
     return wl::bc_vec(u, G, d.uBC, d.exitBC, d.perdir_mask, s);
   }
   int predict(hipStream_t s, const float* dt_dev = nullptr) {                            // mom_predict! src/Flow.jl:190-196 (dt_dev: Δt still on the device — lazydt_ok() paths only)
@@ -414,7 +429,7 @@ struct wl_sim {
       return bc_u(s);
     }
     bool fused_conv = false;
-    if (us && !d.has_body && !forcing && !sgs_model) {   // conv_diff!(f,u⁰) + BDIM! in one launch (u⁰ is the advecting field, u the output)
+    if (fused_nobody_conv()) {   // conv_diff!(f,u⁰) + BDIM! in one launch (u⁰ is the advecting field, u the output)
       ProfScope pc(WL_PROF_CONVDIFF, s);
       if (use_convz && wl::conv_z_ok(G, d.perdir_mask)) {
         WL_TRY(sync_u(s));
@@ -437,7 +452,7 @@ struct wl_sim {
       std::swap(u, us);
       return bc_u(s);
     }
-    if (us && !d.has_body && !forcing && !sgs_model) {   // the advecting field is u itself: write the new u to the spare array and swap
+    if (fused_nobody_conv()) {   // the advecting field is u itself: write the new u to the spare array and swap
       bool fused_conv = false;
       { ProfScope pc(WL_PROF_CONVDIFF, s);
         if (use_convz && wl::conv_z_ok(G, d.perdir_mask)) {
@@ -466,190 +481,204 @@ struct wl_sim {
   bool resjac_backoff = false;            // (a flow whose residual needs the mean shift on every solve would pay launch + sync + two-kernel path each time); re-armed by update!
   int p_shell = -1;          // ghost shell of p / the spare pressure array: -1 unknown (check before the next fused head), 0 all +0, 1 something else, 2 caller-owned p (never assumed)
   bool use_fuse_cfl = true;  // the corrector's projection tail also produces CFL's σ and max(σ)
-  bool cfl_done = false;
   static constexpr int CFL_SLOT = 5;   // res_f slot of CFL's maximum (not slot 0: a tail queued ahead of the solver's read must leave the head's L∞ there for the log)
   bool use_tailspec = true;  // the projection tail is queued behind the smoother before the host has read the norms, gated on the device by the break test (single GPU)
   long n_tailspec = 0, n_tailspec_armed = 0;   // projection tails that ran gated / solves the gated tail was armed for (the difference: withheld — capped, or the head redone)
-  // p = x/Δt NOT STORED between the solves of a time step (option "pdefer", wl_pdefer.hpp).  The unscaled pressure a projection tail writes has one reader inside
-  // mom_step! / wl_sim_mom_steps — the next projection's head, which multiplies it by its own Δt — so where that head is known to be the fused one on this handle
-  // the tail skips the store (4 of its 32 B/cell) and leaves the divisor here; the head divides on load (same two roundings: same bits).  Anything else that would
-  // read p from memory while the divisor is pending calls materialise_p first (the two-kernel head after a redo or a back-off, wl_sim_phase, wl_sim_field, the force
-  // read-outs, a failed step).  The predictor's tail qualifies when the corrector's head will be fused, the corrector's when another step follows in the same call
-  // (as lazydt: nobody can look in between); the last tail of a call always stores, so a call never returns with the divisor pending.
-  // Pointer parity: p and ps trade places at every head and at every STORING tail; a skipped store is a skipped swap, and materialise_p is that store and swap made
-  // late.  Handle-owned p: wl_sim_field("p") reports whichever array holds the pressure — a single step with one skipped store makes three swaps and ends on
-  // the other array, a K-step call makes 2K + 1.  Caller-owned p (p_home): the results must land in the caller's array, so the LAST step's first tail skips only
-  // if that leaves an even number of swaps to go (the solver's x is then p_home itself); in a multi-step call this gives 2(K−1) skipped stores, in a single step none.
+  // p = x/Δt NOT STORED between the solves of a time step (option "pdefer", wl_pdefer.hpp, df.p_scale_pending).  The unscaled pressure a projection tail writes has
+  // one reader inside mom_step! / wl_sim_mom_steps — the next projection's head, which multiplies it by its own Δt — so where that head is known to be the fused one
+  // the tail skips the store (4 of its 32 B/cell) and leaves the divisor; the head divides on load (same two roundings: same bits).  Every other reader calls
+  // materialise_p first.  skip_p_now() says which tails qualify; the last tail of a call always stores, so a call never returns with the divisor pending.
+  // Pointer parity: every head and every STORING tail calls swap_p(); a skipped store is a skipped swap_p(), and materialise_p is that store and swap made late.
+  // Handle-owned p: wl_sim_field("p") reports whichever array holds the pressure — a single step with one skipped store makes three swaps and ends on the other
+  // array, a K-step call makes 2K + 1.  Caller-owned p (p_home): the results must land in the caller's array, so the LAST step's first tail skips only if that
+  // leaves an even number of swaps to go (the solver's x is then p_home itself); in a multi-step call this gives 2(K−1) skipped stores, in a single step none.
   // Should a redo in that last step break the parity after all, mom_step copies the pressure home (one D2D copy, mean-shift flows on caller-owned arrays only).
   bool use_pdefer = true;
-  float p_scale_pending = 0.f;   // ≠ 0: `p` holds the solver's scaled x, the pressure is p / p_scale_pending
   long n_pdefer = 0;             // tails that skipped the store
   float* p_home = nullptr;       // caller-owned p
   // the projection tails with four cells per thread and 16-byte accesses (option "tailwide", k_project_wide in wl_poisson.hip): the same statements per cell, the
   // same launches; taken where the launchers find that the shape and the arrays allow it (they report it: BcFold::wide_ran), everything else runs the one- and two-cell kernels
   bool use_tailwide = true;
   long n_tailwide = 0;           // tails that ran in that form
+  // not fused_nobody_conv(): nothing between a tail and the next head goes through the spare velocity array, so `us` is not asked for
   bool pdefer_ok() const { return use_pdefer && in_step && !sgs_model && !forcing && !d.has_body && head_fused_ok(); }   // (head_fused_ok: no slab, store_f, exitBC, periodic direction, body, back-off)
+  void swap_p() { std::swap(p, ps); mg->lv[0].x = p; }      // the pressure pair trades places: `p` is always the array the solver and the next reader take
   int materialise_p(hipStream_t s) {
-    if (p_scale_pending == 0.f) return 0;
-    const float dp = p_scale_pending; p_scale_pending = 0.f;
-    WL_TRY(wl::div_scalar_to(ps, p, dp, (size_t)G.cs, s));
-    std::swap(p, ps); mg->lv[0].x = p;
+    if (df.p_scale_pending == 0.f) return 0;
+    WL_TRY(wl::div_scalar_to(ps, p, std::exchange(df.p_scale_pending, 0.f), (size_t)G.cs, s));
+    swap_p();
     return 0;
   }
-  int project(float w, hipStream_t s, bool with_cfl = false, bool defer_tail = false, bool more_follow = false) {    // mom_project! :223-232 (defer_tail: inside mom_step!, the corrector follows; more_follow: another step does)
-    const float dtl = w * dt.back();
-    cfl_done = false;
-    if (p_scale_pending != 0.f && !head_fused_ok()) WL_TRY(materialise_p(s));             // (the fused head was switched off since the tail ran: back-off, an option)
-    WL_TRY(sync_u(s));                                                                     // div(u) reads the halo planes
-    if (bc_deferred && !head_fused_ok()) WL_TRY(flush_bc(s));                              // (cannot happen: the deferral tested the same condition — kept as the invariant's guard)
-    if (ps && use_fuse_p && !(comm && d.perdir_mask)) {   // (z-slabs: p's ghost planes are current — exchanged at the end of the last solve, scaled with the rest)
-      WL_TRY(wl::bc_per_scalar(p, G, d.perdir_mask, s));                                   // residual!: perBC!(x) :93 (copies commute with the scaling)
-      // head: z=div(u); x.*=dt; residual! in one pass — the scaled pressure goes to the spare array, which becomes p
-      wl_mg::Level& l0 = mg->lv[0];
-      bool head_done = false;
-      double pre_r1 = 0.0; float pre_rinf = 0.f;
-      bool solved = false;      // the speculative solve behind the fused head stood
-      // ---- the tail, as a function of a device flag (go != nullptr: queued inside the solver loop ahead of its read — runs iff the flag says "converged")
-      const bool split = l0.part && mg->use_zsplit && !comm;        // a body: the three plane ranges of the z-split (see above)
-      const int zm = 4, zna = split ? std::max(l0.g.k0, l0.za - zm) : 0, znb = split ? std::min(l0.g.k1, l0.zb + zm + 1) : 0;
-      int tail_kind = 0;        // 1: projection + flux_out + max σ into the spare array, 2: projection in place, 3: left to the corrector's loader
-      bool tail_stood = false;
-      bool tail_wide = false;      // the tail launched last took the four-cells-per-thread form
-      bool tail_skips_p = false;   // the tail launched last left p = x/Δt to the next fused head (decided per launch: a gated tail that was withheld is launched again)
-      auto skip_p_now = [&]() -> bool {
-        if (!pdefer_ok()) return false;
-        if (with_cfl) return more_follow;                             // the corrector's tail: the next reader is the next step's head
-        if (!defer_tail) return false;                                // the predictor's tail: the corrector's head
-        return !p_home || more_follow || p == p_home;                 // (caller-owned p, last step of the call: see the parity rule above)
-      };
-      auto launch_tail = [&](const float* go) -> int {
-        tail_skips_p = false; tail_wide = false;
-        // (p is the solver's x by now, ps the array the unscaled pressure goes to: both solve() call sites swap before they call)
-        if (with_cfl && use_fuse_cfl && us && !d.exitBC && !d.perdir_mask) {   // + flux_out and its maximum; projected u lands in the spare array
-          tail_kind = 1;
-          if (split) { WL_TRY(flush_bc(s)); WL_TRY(wl::project_cfl_split(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, l0.clp, zna, znb, mg->ws, CFL_SLOT, s, store_f ? 1 : 0)); }
-          else {
-            BcFold fr = fold_req(1);
-            if (bc_deferred && !(fr.on && wl::project_cfl_pair_path(G, l0.cl))) WL_TRY(flush_bc(s));
-            fr.usub = bc_deferred ? 1 : 0;      // flux_out reads the wall-normal boundary faces of the corrector's output: U on load
-            fr.go = go;
-            tail_skips_p = wl::project_cfl_pair_path(G, l0.cl) && skip_p_now();
-            int ran = 0; fr.wide = use_tailwide ? 1 : 0; fr.wide_ran = &ran;
-            WL_TRY(wl::project_cfl(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, mg->ws, CFL_SLOT, s, store_f ? 1 : 0, &fr, tail_skips_p)); bc_folded = fr.on != 0; tail_wide = ran != 0;
-          }
-        } else if (split) { tail_kind = 2; WL_TRY(wl::project_unscale_split(u, mu0, p, ps, G, dtl, l0.cl, l0.clp, zna, znb, s)); }
-        else if (defer_tail && tailfuse_ok()) {   // p = x/Δt now; u −= L∇x and BC! when the corrector reads u (the scaled x stays untouched in the spare pressure array until then)
-          tail_kind = 3;
-          tail_skips_p = skip_p_now();        // (with the store skipped this tail launches nothing at all: the corrector's head takes x with the pending divisor)
-          if (!tail_skips_p) WL_TRY(wl::div_scalar_to(ps, p, dtl, (size_t)G.cs, s));
-        }
-        else { tail_kind = 2; BcFold fr = fold_req(1); fr.go = go; tail_skips_p = skip_p_now();
-               int ran = 0; fr.wide = use_tailwide ? 1 : 0; fr.wide_ran = &ran;
-               WL_TRY(wl::project_unscale(u, mu0, p, ps, G, dtl, l0.cl, s, &fr, tail_skips_p)); bc_folded = fr.on != 0; tail_wide = ran != 0; }
-        return 0;
-      };
-      // the forms that honour the flag: the in-place tail and the pair tail with CFL (not the z-split of a body, not the corrector-loader form)
-      const bool tail_gateable = !split && !(defer_tail && tailfuse_ok()) &&
-                                 (!(with_cfl && use_fuse_cfl && us && !d.exitBC && !d.perdir_mask) || (wl::project_cfl_pair_path(G, l0.cl) && (!bc_deferred || fold_req(1).on)));
-      if (use_resjac && !resjac_backoff && !d.exitBC && !store_f && !d.perdir_mask && !l0.part && mg->defer_shift && mg->lv.size() > 1 && wl::resjac_ok(G, l0.cl) &&
-          (!comm || (l0.dist && mg->x_halo_depth >= 2))) {   // (exitBC: the convective exit leaves a net flux imbalance to the solver's tolerance — the shift is usually due; z-slab: p's ghost planes are current two deep)
-        // head + the V-cycle's first Jacobi!(fine) in one launch, assuming residual!'s mean shift is not due (wl_resjac.hip); Σr decides
-        { ProfScope pr(WL_PROF_RESIDUAL, s);
-          // p's and the spare's ghost cells are +0 unless someone wrote them from outside (checked once after a pointer to p was handed out): no shell pass then
-          if (comm) p_shell = 1;   // (a slab's ghost planes hold the neighbours' pressure: always scaled with the rest)
-          if (p_shell < 0) p_shell = (wl::shell_nonzero(p, G, (int*)(mg->ws.res_f + 7), s) || wl::shell_nonzero(ps, G, (int*)(mg->ws.res_f + 7), s)) ? 1 : 0;
-          WL_TRY(wl::resjac(ps, l0.eps, p, u, G, dtl, 1.f, l0.cl, mg->ws, 1, 0, s, p_shell != 0, bc_deferred ? d.uBC : nullptr, p_scale_pending)); }
-        if (use_headspec && !comm && itmx >= 1) {
-          // solver! runs its V-cycle at least once whatever the initial norms are (src/MultiLevelPoisson.jl:113-123), so Σr is not needed before the first cycle is
-          // queued: the cycle is launched behind the head at once and Σr comes back with the first iteration's norms (one host round trip per solve fewer, no idle
-          // GPU while the host decides).  If the shift turns out to be due, that solve is discarded — the head's inputs are untouched — and the two-kernel path taken.
-          std::swap(p, ps); l0.x = p;
-          std::swap(l0.r, l0.eps);
-          mg->jacobi0_done = true;
-          // armed: the device decides whether the head stands (k_decide: −1 = shift due; the resjac=2/3 hook declares it due there too), the host reads that flag
-          struct SpecClear { wl_mg* m; ~SpecClear() { m->spec_tail = nullptr; m->spec_check_head = 0; } } spec_clear{mg};   // the hook captures this frame: never outlives it
-          if (use_tailspec && tail_gateable) { mg->spec_tail = launch_tail; mg->spec_check_head = resjac_force_redo ? 2 : 1; n_tailspec_armed++; }
-          WL_TRY(mg->solve(2e-3, itmx, nullptr, nullptr, nullptr, s, true, nullptr, nullptr));
-          tail_stood = mg->tail_stood; if (tail_stood) n_tailspec++;
-          const bool due = mg->head_decided ? mg->head_due : (resjac_force_redo || wl_shift_due(mg->first_hd0, (double)wl_ninside_global(mg->lv[0].g)));
-          if (!due) { head_done = true; solved = true; n_resjac++; resjac_redo_run = 0; }
-          else {
-            std::swap(l0.r, l0.eps); std::swap(p, ps); l0.x = p;
-            mg->n.pop_back(); mg->jacobi0_done = false;
-            n_resjac_redo++;
-            if (!resjac_force_redo && ++resjac_redo_run >= 3) resjac_backoff = true;
-          }
-        } else {
-        WL_TRY(wl::combine_results(comm, mg->ws, s));            // z-slabs: Σr, L₁ (sums) and L∞ (max) over the ranks — every rank takes the same branch below
-        double hd2[2]; WL_TRY(wl::read_results(mg->ws, hd2, 2, &pre_rinf, 1, s));
-        const double sr = hd2[0]; pre_r1 = hd2[1];
-        if (!wl_shift_due(sr, (double)wl_ninside_global(mg->lv[0].g)) && !resjac_force_redo) {                                       // src/Poisson.jl:96: no shift — the fused results stand
-          std::swap(p, ps); l0.x = p;
-          std::swap(l0.r, l0.eps);
-          mg->jacobi0_done = true; head_done = true; n_resjac++; resjac_redo_run = 0;
-        } else {                                                                           // shift due: the inputs are untouched, take the two-kernel path
-          n_resjac_redo++;
-          if (!resjac_force_redo && ++resjac_redo_run >= 3) resjac_backoff = true;
-        }
-        }
-      }
-      if (head_done) p_scale_pending = 0.f;      // the head took the pending divisor on load
-      if (!head_done) {
-        WL_TRY(materialise_p(s)); // … and reads p as the unscaled pressure (after a discarded solve p is the scaled x again, untouched: the head only read it)
-        WL_TRY(flush_bc(s));      // the two-kernel head reads u's boundary faces from memory
-        ProfScope pr(WL_PROF_RESIDUAL, s);
-        if (l0.part && mg->use_zsplit && !comm) {   // a body: coefficients from the position on the plane ranges away from it (as in smooth!)
-          const int m = 4, na = std::max(l0.g.k0, l0.za - m), nb = std::min(l0.g.k1, l0.zb + m + 1);
-          WL_TRY(wl::div_residual_split(store_f ? sigma : nullptr, ps, l0.r, p, u, mu0, l0.D, l0.iD, G, dtl, mg->ws, l0.cl, l0.clp, na, nb, s));
-        } else WL_TRY(wl::div_residual(store_f ? sigma : nullptr, ps, l0.r, p, u, mu0, l0.D, l0.iD, G, dtl, mg->ws, l0.cl, s));
-      }
-      if (!head_done) { std::swap(p, ps); l0.x = p; }
-      if (!solved) WL_TRY(mg->solve(2e-3, itmx, nullptr, nullptr, nullptr, s, true, head_done ? &pre_r1 : nullptr, head_done ? &pre_rinf : nullptr));
-      // tail: u -= L∇x ; x./=dt in one pass — the unscaled pressure goes back to the original array
-      if (!tail_stood) WL_TRY(launch_tail(nullptr));
-      if (tail_kind == 3) {   // deferred into the corrector's loader (tailfuse)
-        bc_deferred = false;                  // (the corrector's loader reads this u through the projection AND BC!: nothing in memory is missing)
-        proj_pending = p;
-        if (tail_skips_p) { p_scale_pending = dtl; n_pdefer++; }
-        else { std::swap(p, ps); l0.x = p; }
-        n_tailfuse++;
-        return 0;
-      }
-      if (tail_kind == 1) {
-        bc_deferred = false;                  // the folded stores wrote every boundary location of the new u
-        WL_TRY(wl::combine_results(comm, mg->ws, s));   // max over ranks — issued BEFORE the u exchange starts on the other stream, so that
-        std::swap(u, us); cfl_done = true;              // exchange stays in flight across the Δt read-back and the next predictor's interior
-      }
-      if (tail_wide) n_tailwide++;
-      if (tail_skips_p) { p_scale_pending = dtl; n_pdefer++; }      // p stays the solver's x; no store, no swap
-      else { std::swap(p, ps); l0.x = p; }
-      bc_deferred = false;      // the tails update a cell from its own value only; whatever BC! had not been applied is applied now (folded stores or bc_u)
-      return bc_u(s);
+  // ---- mom_project! :223-232 in stages: head -> solve -> tail -> finish.  Who calls, by name:
+  struct ProjCall {
+    float w; bool with_cfl, corrector_follows, step_follows;      // Δt weight; the tail also produces CFL's maximum; inside mom_step!, the corrector reads u next; another step of the same call does
+    static ProjCall step_first(bool more_follow) { return {1.f, false, true, more_follow}; }
+    static ProjCall step_second(bool more_follow) { return {0.5f, true, false, more_follow}; }
+    static ProjCall bare(float w) { return {w, false, false, false}; }                    // wl_sim_phase 2 and 4: CFL is a phase of its own, every tail is launched and stores
+    static ProjCall score(float w, bool with_cfl) { return {w, with_cfl, false, false}; }    // placement trials: outside in_step, counters reset afterwards
+  };
+  struct ZSplit { bool on; int na, nb; };      // a body: the plane range [na, nb) around it takes the general-coefficient kernels, the ranges below and above the constant-coefficient ones (as in smooth!)
+  ZSplit zsplit() const {
+    const wl_mg::Level& l0 = mg->lv[0]; const int zm = 4; const bool on = l0.part && mg->use_zsplit && !comm;
+    return {on, on ? std::max(l0.g.k0, l0.za - zm) : 0, on ? std::min(l0.g.k1, l0.zb + zm + 1) : 0};
+  }
+  // the tail's form, decided once per projection (before the head: it reads df.bc_deferred as the head will find it)
+  //   PairCfl        u −= L∇x, flux_out and its maximum into the spare velocity array (the pair kernels; with a body: their z-split form)
+  //   InPlace        u −= L∇x and p = x/Δt in place
+  //   SplitInPlace   the same on the three plane ranges of a body
+  //   Loader         left to the corrector's loader ("tailfuse"): at most p = x/Δt is launched here
+  enum class Tail { PairCfl, InPlace, SplitInPlace, Loader };
+  struct TailPlan { Tail form; ZSplit z; bool gateable; };      // gateable: the form honours a device flag `go` (queued ahead of the solver's convergence read, "tailspec")
+  struct TailDone { int wide = 0; bool skips_p = false; };      // what the launch did: ran four cells per thread (the launcher's report, BcFold::wide_ran) / left p = x/Δt to the next fused head
+  bool pair_tail_cfl(bool with_cfl) const { return with_cfl && use_fuse_cfl && us && !d.exitBC && !d.perdir_mask; }
+  TailPlan plan_tail(const ProjCall& c) const {
+    TailPlan t; t.z = zsplit();
+    t.form = pair_tail_cfl(c.with_cfl) ? Tail::PairCfl : t.z.on ? Tail::SplitInPlace : (c.corrector_follows && tailfuse_ok()) ? Tail::Loader : Tail::InPlace;
+    t.gateable = t.form == Tail::InPlace || (t.form == Tail::PairCfl && !t.z.on && wl::project_cfl_pair_path(G, mg->lv[0].cl) && (!df.bc_deferred || fold_req(1).on));
+    return t;
+  }
+  bool skip_p_now(const ProjCall& c) const {      // decided per launch: a back-off during the head withdraws it
+    if (!pdefer_ok()) return false;
+    if (c.with_cfl) return c.step_follows;                          // the corrector's tail: the next reader is the next step's head
+    return c.corrector_follows && (!p_home || c.step_follows || p == p_home);   // the predictor's tail: the corrector's head (caller-owned p, last step of the call: see the parity rule above)
+  }
+  // go != nullptr: queued inside the solver loop ahead of its read — runs iff the flag says "converged"; a gated tail that was withheld is launched again with go = nullptr.
+  // (p is the solver's x by now, ps the array the unscaled pressure goes to: every head has called swap_p())
+  int launch_tail(const TailPlan& plan, const ProjCall& c, float dtl, const float* go, TailDone* done, hipStream_t s) {
+    const wl_mg::Level& l0 = mg->lv[0];
+    *done = TailDone{};
+    BcFold fr = fold_req(1); fr.go = go;
+    fr.wide = use_tailwide ? 1 : 0; fr.wide_ran = &done->wide;
+    switch (plan.form) {
+      case Tail::PairCfl:
+        if (plan.z.on) { WL_TRY(flush_bc(s)); WL_TRY(wl::project_cfl_split(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, l0.clp, plan.z.na, plan.z.nb, mg->ws, CFL_SLOT, s, store_f ? 1 : 0)); break; }
+        if (df.bc_deferred && !(fr.on && wl::project_cfl_pair_path(G, l0.cl))) WL_TRY(flush_bc(s));
+        fr.usub = df.bc_deferred ? 1 : 0;      // flux_out reads the wall-normal boundary faces of the corrector's output: U on load
+        done->skips_p = wl::project_cfl_pair_path(G, l0.cl) && skip_p_now(c);
+        WL_TRY(wl::project_cfl(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, mg->ws, CFL_SLOT, s, store_f ? 1 : 0, &fr, done->skips_p)); df.bc_folded = fr.on != 0;
+        break;
+      case Tail::SplitInPlace: WL_TRY(wl::project_unscale_split(u, mu0, p, ps, G, dtl, l0.cl, l0.clp, plan.z.na, plan.z.nb, s)); break;
+      case Tail::Loader:        // (with the store skipped this tail launches nothing at all: the corrector's head takes x with the pending divisor)
+        done->skips_p = skip_p_now(c);
+        if (!done->skips_p) WL_TRY(wl::div_scalar_to(ps, p, dtl, (size_t)G.cs, s));
+        break;
+      case Tail::InPlace:
+        done->skips_p = skip_p_now(c);
+        WL_TRY(wl::project_unscale(u, mu0, p, ps, G, dtl, l0.cl, s, &fr, done->skips_p)); df.bc_folded = fr.on != 0;
+        break;
     }
-    WL_TRY(materialise_p(s));      // (guard: nothing defers on a handle that takes this path)
-    WL_TRY(flush_bc(s));
+    return 0;
+  }
+  // what a head leaves for project(): the fused results stand / its solve too / and the gated tail behind it ran; the norms a read-back brought;
+  // taken: the fused head's outputs are the solver's x and r at the moment (a speculative solve runs, or ran, on them)
+  struct Head { bool stood = false, solved = false, tail_ran = false, taken = false; double pre_r1 = 0.0; float pre_rinf = 0.f; };
+  void head_swap() { swap_p(); std::swap(mg->lv[0].r, mg->lv[0].eps); }      // x·Δt in the spare pressure array, r in ϵ's <-> the solver's x and r: undoes itself
+  void head_take(Head* h) { head_swap(); mg->jacobi0_done = h->taken = true; }
+  void head_accept(Head* h) {      // no mean shift (src/Poisson.jl:96): the fused results stand — and the head took a pending divisor on load
+    if (!h->taken) head_take(h);
+    n_resjac++; resjac_redo_run = 0; h->stood = true; df.p_scale_pending = 0.f;
+  }
+  void head_discard(Head* h) {     // the shift was due: the head's inputs are untouched, the two-kernel head follows; a speculative solve is forgotten
+    if (h->taken) { head_swap(); mg->jacobi0_done = h->taken = false; mg->n.pop_back(); }
+    n_resjac_redo++;
+    if (!resjac_force_redo && ++resjac_redo_run >= 3) resjac_backoff = true;
+  }
+  // solver! runs its V-cycle at least once whatever the initial norms are (src/MultiLevelPoisson.jl:113-123), so Σr is not needed before the first cycle is
+  // queued: the cycle is launched behind the head at once and Σr comes back with the first iteration's norms (one host round trip per solve fewer, no idle
+  // GPU while the host decides).  If the shift turns out to be due, that solve is discarded.
+  int head_speculate(const ProjCall& c, float dtl, const TailPlan& plan, TailDone* done, Head* h, hipStream_t s) {
+    head_take(h);
+    // armed: the device decides whether the head stands (k_decide: −1 = shift due; the resjac=2/3 hook declares it due there too), the host reads that flag
+    struct SpecClear { wl_mg* m; ~SpecClear() { m->spec_tail = nullptr; m->spec_check_head = 0; } } spec_clear{mg};   // the hook captures this frame: never outlives it
+    if (use_tailspec && plan.gateable) {
+      mg->spec_tail = [&, dtl, done, s](const float* go) { return launch_tail(plan, c, dtl, go, done, s); };
+      mg->spec_check_head = resjac_force_redo ? 2 : 1; n_tailspec_armed++;
+    }
+    WL_TRY(mg->solve(2e-3, itmx, nullptr, nullptr, nullptr, s, true, nullptr, nullptr));
+    h->tail_ran = mg->tail_stood; if (h->tail_ran) n_tailspec++;
+    const bool due = mg->head_decided ? mg->head_due : (resjac_force_redo || wl_shift_due(mg->first_hd0, (double)wl_ninside_global(mg->lv[0].g)));
+    if (due) head_discard(h); else { head_accept(h); h->solved = true; }
+    return 0;
+  }
+  int head_read_back(Head* h, hipStream_t s) {
+    WL_TRY(wl::combine_results(comm, mg->ws, s));            // z-slabs: Σr, L₁ (sums) and L∞ (max) over the ranks — every rank takes the same branch below
+    double hd2[2]; WL_TRY(wl::read_results(mg->ws, hd2, 2, &h->pre_rinf, 1, s));
+    h->pre_r1 = hd2[1];
+    if (!wl_shift_due(hd2[0], (double)wl_ninside_global(mg->lv[0].g)) && !resjac_force_redo) head_accept(h);
+    else head_discard(h);
+    return 0;
+  }
+  // head + the V-cycle's first Jacobi!(fine) in one launch, assuming residual!'s mean shift is not due (wl_resjac.hip); Σr decides
+  int head_fused(const ProjCall& c, float dtl, const TailPlan& plan, TailDone* done, Head* h, hipStream_t s) {
+    { ProfScope pr(WL_PROF_RESIDUAL, s);
+      // p's and the spare's ghost cells are +0 unless someone wrote them from outside (checked once after a pointer to p was handed out): no shell pass then
+      if (comm) p_shell = 1;   // (a slab's ghost planes hold the neighbours' pressure: always scaled with the rest)
+      if (p_shell < 0) p_shell = (wl::shell_nonzero(p, G, (int*)(mg->ws.res_f + 7), s) || wl::shell_nonzero(ps, G, (int*)(mg->ws.res_f + 7), s)) ? 1 : 0;
+      WL_TRY(wl::resjac(ps, mg->lv[0].eps, p, u, G, dtl, 1.f, mg->lv[0].cl, mg->ws, 1, 0, s, p_shell != 0, df.bc_deferred ? d.uBC : nullptr, df.p_scale_pending)); }
+    return use_headspec && !comm && itmx >= 1 ? head_speculate(c, dtl, plan, done, h, s) : head_read_back(h, s);
+  }
+  // z=div(u); x.*=dt; residual! — the scaled pressure goes to the spare array, which becomes p.  After a discarded solve p is the scaled x again, untouched: the head only read it
+  int head_two_kernel(float dtl, hipStream_t s) {
+    wl_mg::Level& l0 = mg->lv[0];
+    WL_TRY(settle(s));            // reads p as the unscaled pressure and u's boundary faces from memory
+    { ProfScope pr(WL_PROF_RESIDUAL, s);
+      const ZSplit z = zsplit();
+      if (z.on) WL_TRY(wl::div_residual_split(store_f ? sigma : nullptr, ps, l0.r, p, u, mu0, l0.D, l0.iD, G, dtl, mg->ws, l0.cl, l0.clp, z.na, z.nb, s));
+      else WL_TRY(wl::div_residual(store_f ? sigma : nullptr, ps, l0.r, p, u, mu0, l0.D, l0.iD, G, dtl, mg->ws, l0.cl, s)); }
+    swap_p();
+    return 0;
+  }
+  int project_finish(const TailPlan& plan, const TailDone& done, float dtl, hipStream_t s) {
+    df.bc_deferred = false;     // every form leaves the boundary current: folded stores, the bc_u below, or the corrector's loader, which reads u through the projection AND BC!
+    if (plan.form == Tail::Loader) { df.proj_pending = p; n_tailfuse++; }      // (the scaled x stays untouched in what is the spare pressure array from here on)
+    if (plan.form == Tail::PairCfl) {
+      WL_TRY(wl::combine_results(comm, mg->ws, s));   // max over ranks — issued BEFORE the u exchange starts on the other stream, so that
+      std::swap(u, us); df.cfl_done = true;           // exchange stays in flight across the Δt read-back and the next predictor's interior
+    }
+    if (done.wide) n_tailwide++;
+    if (done.skips_p) { df.p_scale_pending = dtl; n_pdefer++; }      // p stays the solver's x; no store, no swap
+    else swap_p();
+    return plan.form == Tail::Loader ? 0 : bc_u(s);
+  }
+  int project_plain(float dtl, hipStream_t s) {      // no spare pressure array, or fuse_p = 0: the reference's statements one by one
+    WL_TRY(settle(s));             // (guard: nothing defers on a handle that takes this path)
     WL_TRY(wl::div_scale(sigma, p, u, G, dtl, s));                                       // z=div(u); x.*=dt
     WL_TRY(mg->solve(2e-3, itmx, nullptr, nullptr, nullptr, s));
     WL_TRY(wl::project(u, mu0, p, G, s));
     WL_TRY(wl::div_scalar(p, dtl, (size_t)G.cs, s));                                     // x./=dt
     return bc_u(s);
   }
+  int project(const ProjCall& c, hipStream_t s) {
+    const float dtl = c.w * dt.back();
+    df.cfl_done = false;
+    if (df.p_scale_pending != 0.f && !head_fused_ok()) WL_TRY(materialise_p(s));          // (the fused head was switched off since the tail ran: back-off, an option)
+    WL_TRY(sync_u(s));                                                                     // div(u) reads the halo planes
+    if (df.bc_deferred && !head_fused_ok()) WL_TRY(flush_bc(s));                           // (cannot happen: the deferral tested the same condition — kept as the invariant's guard)
+    if (!ps || !use_fuse_p || (comm && d.perdir_mask)) return project_plain(dtl, s);      // (z-slabs: p's ghost planes are current — exchanged at the end of the last solve, scaled with the rest)
+    WL_TRY(wl::bc_per_scalar(p, G, d.perdir_mask, s));                                     // residual!: perBC!(x) :93 (copies commute with the scaling)
+    const TailPlan plan = plan_tail(c);
+    TailDone done; Head h;
+    if (head_fused_path()) WL_TRY(head_fused(c, dtl, plan, &done, &h, s));
+    if (!h.stood) WL_TRY(head_two_kernel(dtl, s));
+    if (!h.solved) WL_TRY(mg->solve(2e-3, itmx, nullptr, nullptr, nullptr, s, true, h.stood ? &h.pre_r1 : nullptr, h.stood ? &h.pre_rinf : nullptr));
+    if (!h.tail_ran) WL_TRY(launch_tail(plan, c, dtl, nullptr, &done, s));      // u -= L∇x ; x./=dt — the unscaled pressure goes back to the original array
+    return project_finish(plan, done, dtl, s);
+  }
   // Δt of the NEXT step left on the device (wl_sim_mom_steps only: more steps follow inside the same call, nobody can look at the history in between): the finaliser
   // of CFL's maximum is followed by a one-thread kernel with mom_step!'s formula, the next predictor reads Δt through a pointer and is queued at once; the host
   // copies the maximum while that predictor runs and appends the same Δt to the history (same statements on the same number: same bits).
-  bool use_lazydt = true, dt_pending = false;
+  bool use_lazydt = true;
   hipEvent_t ev_dt = nullptr;
   bool lazydt_ok() const {      // the next predictor will be the flux-once tiled launch on the single domain
-    return use_lazydt && in_step && !comm && us && !d.has_body && !forcing && !sgs_model && !use_convz && !d.exitBC && !d.perdir_mask && !store_f && wl::conv_flux_on() &&
+    return use_lazydt && in_step && !comm && fused_nobody_conv() && !use_convz && !d.exitBC && !d.perdir_mask && !store_f && wl::conv_flux_on() &&
            wl::conv_tile_ok(G, d.perdir_mask, G.k1 - G.k0) && mg->lv[0].cl.on;
   }
   int cfl(hipStream_t s, bool more_follow = false) {                                     // CFL :234-237
-    if (!cfl_done) { WL_TRY(sync_u(s)); WL_TRY(wl::cfl_dev(u, sigma, G, mg->ws, CFL_SLOT, s)); WL_TRY(wl::combine_results(comm, mg->ws, s)); }   // max over ranks
-    cfl_done = false;
+    if (!df.cfl_done) { WL_TRY(sync_u(s)); WL_TRY(wl::cfl_dev(u, sigma, G, mg->ws, CFL_SLOT, s)); WL_TRY(wl::combine_results(comm, mg->ws, s)); }   // max over ranks
+    df.cfl_done = false;
     if (more_follow && lazydt_ok()) {
       hipLaunchKernelGGL(k_dt_from_cfl, dim3(1), dim3(1), 0, s, mg->ws.res_f, CFL_SLOT, CFL_SLOT + 1, d.nu);
-      dt_pending = true;
+      df.dt_pending = true;
       return 0;
     }
     float hf6[CFL_SLOT + 1]; WL_TRY(wl::read_results(mg->ws, nullptr, 0, hf6, CFL_SLOT + 1, s)); const float mx = hf6[CFL_SLOT];
@@ -658,10 +687,13 @@ struct wl_sim {
   }
   int mom_step(hipStream_t s, bool more_follow = false) {
     const int rc = mom_step_body(s, more_follow);
-    if (rc != 0) { bc_deferred = false; dt_pending = false; (void)materialise_p(s); p_scale_pending = 0.f; return rc; }   // a failed step leaves no deferred BC!, no Δt on the device and no pending divisor for the next call to take
+    // A failed step leaves nothing pending for the next call to take.  BC! of a u nobody can use is dropped, not launched.
+    // The divisor is applied: pdefer is single-domain, so settle's slab wait, the only step before it, does nothing there.
+    // On slabs that wait (no launch) lets the exchange finish before its flag goes; the rest of the record is cleared.
+    if (rc != 0) { df.bc_deferred = false; (void)settle(s); df = Deferred{}; return rc; }
     if (!more_follow && p_home && p != p_home) {      // caller-owned p that ended on the spare array (a redo inside the last step): copy it home
       WL_HIP(hipMemcpyAsync(p_home, p, sizeof(float) * (size_t)G.cs, hipMemcpyDeviceToDevice, s));
-      ps = p; p = p_home; mg->lv[0].x = p;
+      swap_p();      // (the pair is {p_home, spare}: ps was p_home)
     }
     return rc;
   }
@@ -672,18 +704,17 @@ struct wl_sim {
     if (swap_ok) { std::swap(u, u0); if (d.exitBC) WL_TRY(copy_exit_face(u, u0, s)); }   // (an exchange still in flight belongs to the array that is now u⁰ — the predictor's advecting field)
     else { WL_TRY(sync_u(s)); WL_HIP(hipMemcpyAsync(u0, u, sizeof(float) * (size_t)G.cs * d.D, hipMemcpyDeviceToDevice, s)); }   // u⁰ .= u
     struct InStep { bool& f; InStep(bool& b) : f(b) { f = true; } ~InStep() { f = false; } } guard(in_step);
-    if (dt_pending) {   // the CFL maximum of the previous step is copied back between ITS finaliser and THIS predictor, which takes Δt from the device
+    if (df.dt_pending) {   // the CFL maximum of the previous step is copied back between ITS finaliser and THIS predictor, which takes Δt from the device
       if (!ev_dt) WL_HIP(hipEventCreateWithFlags(&ev_dt, hipEventDisableTiming));
       double hd1[1]; float hf7[CFL_SLOT + 2];
       WL_TRY(wl::read_results_overlapped(mg->ws, hd1, 1, hf7, CFL_SLOT + 2, s, ev_dt, [&]() -> int { return predict(s, mg->ws.res_f + CFL_SLOT + 1); }));
       dt.push_back(std::fmin(10.f, 1.0f / (hf7[CFL_SLOT] + 5 * d.nu)));
-      dt_pending = false;
+      df.dt_pending = false;
     } else
     WL_TRY(predict(s));
-    WL_TRY(project(1.f, s, false, true, more_follow));
+    WL_TRY(project(ProjCall::step_first(more_follow), s));
     WL_TRY(correct(s));
-    WL_TRY(project(0.5f, s, true, false, more_follow));
-    WL_TRY(flush_bc(s));      // (nothing is pending here: every projection ends with BC! applied — guard)
+    WL_TRY(project(ProjCall::step_second(more_follow), s));
     return cfl(s, more_follow);
   }
 };
@@ -707,30 +738,26 @@ int wl_sim::exit_bc(hipStream_t s) {
     WL_LAUNCH_CHECK();
     return wl::halo(comm, u, G, d.D, 2, s);      // the exit face changed after BC!'s exchange
   }
-  double* sc = mg->ws.res_d + 4;
-  const long cnt = (long)(G.ny - 2) * (G.D == 3 ? (G.nz - 2) : 1);
-  const unsigned nb = (unsigned)((cnt + WL_BLOCK - 1) / WL_BLOCK);
-  DSEL(G.D, k_exit_facesum, dim3(1), dim3(1024), 0, s, G, u, sc, 0);
-  DSEL(G.D, k_exit_update, dim3(nb), dim3(WL_BLOCK), 0, s, G, u, u0, sc, dt.back(), 0);
-  DSEL(G.D, k_exit_facesum, dim3(1), dim3(1024), 0, s, G, u, sc, 1);
-  DSEL(G.D, k_exit_update, dim3(nb), dim3(WL_BLOCK), 0, s, G, u, u0, sc, dt.back(), 1);
-  WL_LAUNCH_CHECK(); return 0;
+  return exit_bc_single(G, u, u0, mg->ws.res_d + 4, dt.back(), s);
 }
 
+// exitBC!(u,u⁰,Δt) on a single domain (src/core.jl:226-233): inflow mean -> convective update of the exit face (mode 0), its mean -> flux correction (mode 1)
+int wl_sim::exit_bc_single(const GridX& G, float* u, const float* u0, double* sc, float dt, hipStream_t s) {
+  const long cnt = (long)(G.ny - 2) * (G.D == 3 ? (G.nz - 2) : 1);
+  const unsigned nb = (unsigned)((cnt + WL_BLOCK - 1) / WL_BLOCK);
+  for (int mode = 0; mode < 2; mode++) {
+    DSEL(G.D, k_exit_facesum, dim3(1), dim3(1024), 0, s, G, (const float*)u, sc, mode);
+    DSEL(G.D, k_exit_update, dim3(nb), dim3(WL_BLOCK), 0, s, G, u, u0, sc, dt, mode);
+  }
+  WL_LAUNCH_CHECK(); return 0;
+}
 extern "C" {
 
 int wl_exit_bc(float* u, const float* u0, const wl_grid* g, float dt, void* st) {
   WL_CHECK(wl_grid_ok(g), "bad wl_grid"); WL_CHECK(g->D == 2 || g->nz == g->gnz, "exitBC! needs the whole x-exit face on one rank");
   WL_TRY(wl_ctx_ensure());
   const GridX G = gx(*g); hipStream_t s = wl_stream(st);
-  double* sc = wl_red_ws(wl_ctx().red).res_d + 4;
-  const long cnt = (long)(G.ny - 2) * (G.D == 3 ? (G.nz - 2) : 1);
-  const unsigned nb = (unsigned)((cnt + WL_BLOCK - 1) / WL_BLOCK);
-  DSEL(G.D, k_exit_facesum, dim3(1), dim3(1024), 0, s, G, (const float*)u, sc, 0);
-  DSEL(G.D, k_exit_update, dim3(nb), dim3(WL_BLOCK), 0, s, G, u, u0, sc, dt, 0);
-  DSEL(G.D, k_exit_facesum, dim3(1), dim3(1024), 0, s, G, (const float*)u, sc, 1);
-  DSEL(G.D, k_exit_update, dim3(nb), dim3(WL_BLOCK), 0, s, G, u, u0, sc, dt, 1);
-  WL_LAUNCH_CHECK(); return 0;
+  return wl_sim::exit_bc_single(G, u, u0, wl_red_ws(wl_ctx().red).res_d + 4, dt, s);
 }
 int wl_L2_inside(const float* a, const wl_grid* g, double* out, void* st) {
   WL_CHECK(wl_grid_ok(g), "bad wl_grid"); WL_TRY(wl_ctx_ensure());
@@ -818,13 +845,13 @@ static int sim_create_common(wl_sim** out, const wl_sim_desc* desc, wl_comm* com
 static double placement_score(wl_sim* s) {
   hipStream_t q = 0;
   const size_t n0 = s->mg->n.size();
-  if (s->project(1.f, q) != 0) return 1e30;            // warm-up (first-launch costs)
+  if (s->project(wl_sim::ProjCall::score(1.f, false), q) != 0) return 1e30;            // warm-up (first-launch costs)
   if (hipStreamSynchronize(q) != hipSuccess) return 1e30;
   hipEvent_t a, b; if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return 1e30;
   float ms = 1e30f; int rc = 0;
   for (int rep = 0; rep < 2 && rc == 0; rep++) {        // the faster of two timed pairs (each holds host read-backs of the solver)
     (void)hipEventRecord(a, q);
-    rc = s->project(1.f, q); if (rc == 0) rc = s->project(0.5f, q, true);
+    rc = s->project(wl_sim::ProjCall::score(1.f, false), q); if (rc == 0) rc = s->project(wl_sim::ProjCall::score(0.5f, true), q);
     (void)hipEventRecord(b, q); (void)hipEventSynchronize(b);
     float t = 1e30f; (void)hipEventElapsedTime(&t, a, b);
     if (t < ms) ms = t;
@@ -832,7 +859,7 @@ static double placement_score(wl_sim* s) {
   (void)hipEventDestroy(a); (void)hipEventDestroy(b);
   // back to the state of a fresh handle: pois.n, counters, Δt untouched by mom_project!; u, p are still zero (BC! wrote the boundary values the
   // initial condition / init_flow will write again)
-  s->mg->n.resize(n0); s->n_resjac = 0; s->n_resjac_redo = 0; s->resjac_redo_run = 0; s->resjac_backoff = false; s->cfl_done = false;
+  s->mg->n.resize(n0); s->n_resjac = 0; s->n_resjac_redo = 0; s->resjac_redo_run = 0; s->resjac_backoff = false; s->df.cfl_done = false;
   s->mg->log_r1.clear(); s->mg->log_rinf.clear(); s->mg->log_w.clear();
   return rc == 0 ? (double)ms : 1e30;
 }
@@ -869,8 +896,7 @@ int wl_sim_create_slab(wl_sim** out, const wl_sim_desc* desc, wl_comm* comm) { r
 int wl_sim_destroy(wl_sim* s) { delete s; return 0; }
 float* wl_sim_field(wl_sim* s, const char* name) {
   const std::string n(name);
-  (void)s->sync_u(0);        // the caller is about to read or write the arrays: finish an exchange that is still in flight
-  if (n == "p") (void)s->materialise_p(0);      // (a call never returns with the divisor pending: guard)
+  (void)s->settle(0);        // the caller is about to read or write the arrays: finish an exchange that is still in flight (the rest is a guard: nothing else is pending between calls)
   if (n == "V" || n == "mu1" || n == "mu0") s->mask_valid = false;
   if (n == "u") return s->u; if (n == "u0") return s->u0; if (n == "f") return s->f; if (n == "p") { if (s->p_shell != 2) s->p_shell = -1; return s->p; }
   if (n == "sigma") return s->sigma; if (n == "V") return s->V; if (n == "mu0") return s->mu0; if (n == "mu1") return s->mu1;
@@ -994,13 +1020,15 @@ int wl_sim_set_dt_last(wl_sim* s, float dt) { WL_CHECK(s && dt > 0.f, "bad Δt")
 double wl_sim_time(const wl_sim* s) { float t = 0.f; for (size_t k = 0; k + 1 < s->dt.size(); k++) t += s->dt[k]; return (double)t; }
 int wl_sim_phase(wl_sim* s, int phase, void* st) {
   hipStream_t q = wl_stream(st);
-  WL_TRY(s->materialise_p(q));      // (guard, as in wl_sim_field)
+  // settle() without its sync_u: the phases wait for an exchange where they first read the halo planes (the slab predictor overlaps its interior with it)
+  WL_TRY(s->materialise_p(q));      // (guards, as in wl_sim_field)
+  WL_TRY(s->flush_bc(q));
   switch (phase) {
     case 0: WL_TRY(s->sync_u(q)); WL_HIP(hipMemcpyAsync(s->u0, s->u, sizeof(float) * (size_t)s->G.cs * s->d.D, hipMemcpyDeviceToDevice, q)); return wl::scale_u(s->u, s->G, 0.f, q);
     case 1: return s->predict(q);
-    case 2: return s->project(1.f, q);
+    case 2: return s->project(wl_sim::ProjCall::bare(1.f), q);
     case 3: return s->correct(q);
-    case 4: return s->project(0.5f, q);
+    case 4: return s->project(wl_sim::ProjCall::bare(0.5f), q);
     case 5: return s->cfl(q);
   }
   wl_set_error("bad phase"); return WL_EINVAL;
@@ -1094,18 +1122,14 @@ int wl_viscous_moment_body(const float* x0, const float* u, const wl_grid* g, fl
   BodyArg bd; WL_TRY(to_body_arg(g->D, body, &bd));
   return force_reduce(1, u, nu, gx(*g), bd, wl_red_ws(wl_ctx().red), nullptr, out, wl_stream(st), x0);
 }
-int wl_sim_pressure_moment_body(wl_sim* s, const float* x0, const wl_body* body, double* out, void* st) {
-  WL_CHECK(x0, "null x0");
-  WL_TRY(s->materialise_p(wl_stream(st)));
+// the handle's p (which = 0) or u (1) on the body; x0: the moment about that point
+static int sim_force_body(int which, wl_sim* s, const float* x0, const wl_body* body, double* out, void* st) {
   BodyArg bd; WL_TRY(to_body_arg(s->d.D, body, &bd));
-  return force_reduce(0, s->p, 0.f, s->G, bd, s->mg->ws, s->comm, out, wl_stream(st), x0);
+  WL_TRY(s->settle(wl_stream(st)));                  // (∂u/∂z at the slab faces reads the neighbours' planes)
+  return force_reduce(which, which == 0 ? s->p : s->u, which == 0 ? 0.f : s->d.nu, s->G, bd, s->mg->ws, s->comm, out, wl_stream(st), x0);
 }
-int wl_sim_viscous_moment_body(wl_sim* s, const float* x0, const wl_body* body, double* out, void* st) {
-  WL_CHECK(x0, "null x0");
-  BodyArg bd; WL_TRY(to_body_arg(s->d.D, body, &bd));
-  WL_TRY(s->sync_u(wl_stream(st)));
-  return force_reduce(1, s->u, s->d.nu, s->G, bd, s->mg->ws, s->comm, out, wl_stream(st), x0);
-}
+int wl_sim_pressure_moment_body(wl_sim* s, const float* x0, const wl_body* body, double* out, void* st) { WL_CHECK(x0, "null x0"); return sim_force_body(0, s, x0, body, out, st); }
+int wl_sim_viscous_moment_body(wl_sim* s, const float* x0, const wl_body* body, double* out, void* st) { WL_CHECK(x0, "null x0"); return sim_force_body(1, s, x0, body, out, st); }
 int wl_sim_measure_body(wl_sim* s, const wl_body* body, float eps, void* st) {
   WL_CHECK(s->d.has_body && s->mu1 && s->V, "simulation was created with has_body=0");
   BodyArg bd; WL_TRY(to_body_arg(s->d.D, body, &bd));
@@ -1115,16 +1139,8 @@ int wl_sim_measure_body(wl_sim* s, const wl_body* body, float eps, void* st) {
   WL_TRY(s->refresh_body_mask(q));
   return s->mg->update(q);                                                                                                          // WaterLily.jl:148
 }
-int wl_sim_pressure_force_body(wl_sim* s, const wl_body* body, double* out, void* st) {
-  WL_TRY(s->materialise_p(wl_stream(st)));
-  BodyArg bd; WL_TRY(to_body_arg(s->d.D, body, &bd));
-  return force_reduce(0, s->p, 0.f, s->G, bd, s->mg->ws, s->comm, out, wl_stream(st));
-}
-int wl_sim_viscous_force_body(wl_sim* s, const wl_body* body, double* out, void* st) {
-  BodyArg bd; WL_TRY(to_body_arg(s->d.D, body, &bd));
-  WL_TRY(s->sync_u(wl_stream(st)));                  // ∂u/∂z at the slab faces reads the neighbours' planes
-  return force_reduce(1, s->u, s->d.nu, s->G, bd, s->mg->ws, s->comm, out, wl_stream(st));
-}
+int wl_sim_pressure_force_body(wl_sim* s, const wl_body* body, double* out, void* st) { return sim_force_body(0, s, nullptr, body, out, st); }
+int wl_sim_viscous_force_body(wl_sim* s, const wl_body* body, double* out, void* st) { return sim_force_body(1, s, nullptr, body, out, st); }
 int wl_sim_measure_bodyset(wl_sim* s, const wl_bodyset* set, float eps, void* st) {
   WL_CHECK(s, "null wl_sim"); WL_CHECK(s->d.has_body && s->mu1 && s->V, "simulation was created with has_body=0");
   SetArg P; WL_TRY(wl::bodyset_prepare(s->d.D, set, &P));
@@ -1138,8 +1154,7 @@ static int sim_force_bodyset(int which, wl_sim* s, const float* x0, const wl_bod
   WL_CHECK(s && out, "null wl_sim / out");
   SetArg P; WL_TRY(wl::bodyset_prepare(s->d.D, set, &P));
   hipStream_t q = wl_stream(st);
-  if (which == 0) WL_TRY(s->materialise_p(q));
-  if (which == 1) WL_TRY(s->sync_u(q));              // ∂u/∂z at the slab faces reads the neighbours' planes
+  WL_TRY(s->settle(q));                              // (∂u/∂z at the slab faces reads the neighbours' planes)
   const float* a = which == 0 ? s->p : s->u; const float nu = which == 0 ? 0.f : s->d.nu; const GridX& G = s->G;
   return wl::force_reduce_with(G, s->mg->ws, s->comm, out, q,
                                [&](dim3 grid, double* part, hipStream_t qq) { return wl::bodyset_force_partials(which, a, nu, G, P, x0, grid, part, qq); });
