@@ -124,6 +124,27 @@ size_t wl_reduce_workspace_bytes(void);
 int wl_meanflow_update(float* P, float* U, float* UU, const float* p, const float* u, const wl_grid* g, float eps, void* stream);
 int wl_meanflow_uu(float* tau, const float* UU, const float* U, const wl_grid* g, void* stream);   /* uu!(τ,a) :250-252 */
 
+/* ---- flow diagnostics: src/Metrics.jl:27-109 ------------------------------------------------------ */
+/* Whole-field forms of the reference's per-index functions (`@inside σ[I] = f(I,u)`): only inside cells of an output are written, its ghost
+ * cells keep what they held.  u is the (Ng...,D) velocity array; an output may be flow.σ, it may not overlap u (WL_EINVAL).  ke, ω, ω_mag, ω_θ
+ * and λ₂ come from one z-marching kernel that forms J[i][j] = ∂(i,j,I,u) (:42-44) per cell and reads every u value once per tile: one launch
+ * per call, and a field has the same bits whichever entry point produced it.  ω, ω_mag, ω_θ, λ₂ and helicity are CartesianIndex{3} methods:
+ * a 2-D wl_grid returns WL_EINVAL.  Single-domain grids only: a z-slab wl_grid returns WL_EINVAL for every entry point of this section. */
+int wl_ke(float* out, const float* u, const wl_grid* g, const float* host_U /*NULL = 0*/, void* stream);             /* ke(I,u,U) :33-35 (2-D and 3-D) */
+int wl_curl(float* out, const float* u, const wl_grid* g, int i /*1..3; 2-D: 3*/, void* stream);                     /* curl(i,I,u) :68 — the cell-EDGE stencil */
+int wl_omega(float* out3, const float* u, const wl_grid* g, void* stream);                                           /* ω(I,u) :74 — out3 is a vector array (Ng...,3) */
+int wl_omega_mag(float* out, const float* u, const wl_grid* g, void* stream);                                        /* ω_mag(I,u) :80 */
+int wl_omega_theta(float* out, const float* u, const wl_grid* g, const float host_z[3], const float host_center[3], void* stream);   /* ω_θ(I,z,center,u) :87-91 */
+/* λ₂(I,u) :54-58 — J in Float32 (cross terms as neighbour differences first); S²+Ω² and its middle eigenvalue (closed form) in Float64: accurate to a few
+ * eps32·‖S²+Ω²‖ in every cell, where eigenvalues coincide and where the gradient nearly vanishes included; S²+Ω² = 0 gives exactly 0 */
+int wl_lambda2(float* out, const float* u, const wl_grid* g, void* stream);
+int wl_helicity(float* out, const float* u, const float* omega, const wl_grid* g, void* stream);                     /* helicity(I,u,ω) :99-109, ω a collocated (Ng...,3) array */
+/* one pass over u for several fields at once; any NULL output is skipped; at least one non-NULL */
+int wl_flow_fields(const float* u, const wl_grid* g, const float* host_U, float* ke, float* omega3, float* omega_mag, float* lambda2, void* stream);
+/* out = { Σ_inside ke(I,u,U), Σ_inside ½|ω|², max_inside |ω| } (2-D: curl(3,I,u) for ω): the per-cell Float32 values the field calls produce, summed in
+ * Float64; at most two launches; synchronises.  scratch: device workspace of wl_reduce_workspace_bytes() bytes. */
+int wl_flow_stats(const float* u, const wl_grid* g, const float* host_U, double out[3], void* scratch /*NULL = library's*/, void* stream);
+
 /* ---- multigrid transfer: src/MultiLevelPoisson.jl ---------------------------------------------- */
 int wl_restrict(float* a_coarse, const wl_grid* gc, const float* b_fine, const wl_grid* gf, void* stream);    /* restrict! :49 */
 int wl_prolongate(float* a_fine, const wl_grid* gf, const float* b_coarse, const wl_grid* gc, void* stream);  /* prolongate! :50 */
@@ -292,6 +313,11 @@ int wl_sim_viscous_force_body(wl_sim* s, const wl_body* host_body, double out[3]
 /* pressure_force(sim) for that sphere (src/Metrics.jl:116-133): Float64 accumulation, does not touch flow.f */
 int wl_sim_pressure_force_sphere(wl_sim* s, const float* host_center, float R, double* host_out, void* stream);
 int wl_sim_viscous_force_sphere(wl_sim* s, const float* center, float R, double* out, void* stream);   /* viscous_force(sim) src/Metrics.jl:140-154 (single domain) */
+
+/* flow diagnostics (src/Metrics.jl:27-109; wl_flow_stats / wl_flow_fields above) on a handle's CURRENT velocity — roles rotate: the array
+ * wl_sim_field(s,"u") names.  Outputs may be the handle's sigma.  The step path is not touched.  A z-slab handle returns WL_EINVAL. */
+int wl_sim_flow_stats(wl_sim* s, const float* host_U, double out[3], void* stream);
+int wl_sim_flow_fields(wl_sim* s, const float* host_U, float* ke, float* omega3, float* omega_mag, float* lambda2, void* stream);
 
 /* ---- composite bodies: closed-form leaves under rigid maps, combined by set operations (src/Body.jl:91-107, RigidMap.jl) -------
  * A wl_bodyset is a postfix program of at most WL_BODYSET_MAX nodes (evaluation stack at most WL_BODYSET_STACK deep, final depth 1).

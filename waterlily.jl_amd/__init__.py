@@ -8,7 +8,8 @@ from .core import (BC_, CDS, QUICK, VANLEER, L2, exitBC_, inside, jl_zeros, loc,
 from .flow import BDIM_, CFL, Flow, conv_diff_, mom_correct_, mom_predict_, mom_project_, mom_step_, scale_u_, sgs, sgs_, udf_  # noqa: F401
 from .poisson import (pcg_, poisson_solver_, GaussSeidelRB_, Jacobi_, L1, Linf, MultiLevelPoisson, Poisson, increment_, mult_, norms, prolongate_,  # noqa: F401
                       residual_, restrict_, restrictL_, set_diag_, smooth_, update_)
-from .metrics import MeanFlow, load_checkpoint, save_checkpoint  # noqa: F401
+from .metrics import (MeanFlow, curl_, flow_fields_, flow_stats, helicity_, ke_, lambda2_, load_checkpoint, omega_, omega_mag_, omega_theta_,  # noqa: F401
+                      save_checkpoint)
 from .simulation import (FusedSimulation, Simulation, measure_, pressure_force, pressure_moment, viscous_force,  # noqa: F401
                          viscous_moment)
 from . import bodies  # noqa: F401,E402

@@ -101,6 +101,17 @@ SIGNATURES = {
     "wl_project": (i32, [P, P, P, G, P]),
     "wl_cfl": (i32, [P, P, G, f32, f32, C.POINTER(f32), P]),
     "wl_sgs": (i32, [P, P, P, G, f32, f32, P]),
+    "wl_ke": (i32, [P, P, G, C.POINTER(f32), P]),
+    "wl_curl": (i32, [P, P, G, i32, P]),
+    "wl_omega": (i32, [P, P, G, P]),
+    "wl_omega_mag": (i32, [P, P, G, P]),
+    "wl_omega_theta": (i32, [P, P, G, C.POINTER(f32), C.POINTER(f32), P]),
+    "wl_lambda2": (i32, [P, P, G, P]),
+    "wl_helicity": (i32, [P, P, P, G, P]),
+    "wl_flow_fields": (i32, [P, G, C.POINTER(f32), P, P, P, P, P]),
+    "wl_flow_stats": (i32, [P, G, C.POINTER(f32), C.POINTER(f64), P, P]),
+    "wl_sim_flow_stats": (i32, [P, C.POINTER(f32), C.POINTER(f64), P]),
+    "wl_sim_flow_fields": (i32, [P, C.POINTER(f32), P, P, P, P, P]),
     "wl_set_diag": (i32, [P, P, P, G, P]),
     "wl_mult": (i32, [P, P, P, P, G, P]),
     "wl_residual": (i32, [P, P, P, P, P, P, G, P, P]),

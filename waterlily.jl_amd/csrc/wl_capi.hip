@@ -541,6 +541,23 @@ int wl_bdim(float* u, const float* u0, float* f, const float* V, const float* mu
 }
 // sgs!(flow,u,t; νₜ=smagorinsky,S,Cs,Δ)   src/util.jl:66-76 — f = flow.f, sigma = flow.σ (scratch: receives νₜ)
 int wl_sgs(float* f, float* sigma, const float* u, const wl_grid* g, float Cs, float Delta, void* st) { GRID_ARG(g); return wl::sgs(f, sigma, u, G, Cs, Delta, wl_stream(st)); }
+// flow diagnostics   src/Metrics.jl:27-109 (wl_metrics.hip).  The single-field leaves run the instantiations wl_flow_fields runs.
+int wl_flow_fields(const float* u, const wl_grid* g, const float* U, float* ke, float* w3, float* wmag, float* l2, void* st) { GRID_ARG(g); return wl::metrics_fields(u, G, U, ke, w3, wmag, l2, wl_stream(st)); }
+int wl_ke(float* out, const float* u, const wl_grid* g, const float* U, void* st) { WL_CHECK(out, "wl_ke: null output"); return wl_flow_fields(u, g, U, out, nullptr, nullptr, nullptr, st); }
+int wl_omega(float* out3, const float* u, const wl_grid* g, void* st) { WL_CHECK(out3, "wl_omega: null output"); return wl_flow_fields(u, g, nullptr, nullptr, out3, nullptr, nullptr, st); }
+int wl_omega_mag(float* out, const float* u, const wl_grid* g, void* st) { WL_CHECK(out, "wl_omega_mag: null output"); return wl_flow_fields(u, g, nullptr, nullptr, nullptr, out, nullptr, st); }
+int wl_lambda2(float* out, const float* u, const wl_grid* g, void* st) { WL_CHECK(out, "wl_lambda2: null output"); return wl_flow_fields(u, g, nullptr, nullptr, nullptr, nullptr, out, st); }
+int wl_omega_theta(float* out, const float* u, const wl_grid* g, const float* z, const float* c, void* st) { GRID_ARG(g); return wl::metrics_omega_theta(out, u, G, z, c, wl_stream(st)); }
+int wl_curl(float* out, const float* u, const wl_grid* g, int i, void* st) { GRID_ARG(g); return wl::metrics_curl(out, u, G, i, wl_stream(st)); }
+int wl_helicity(float* out, const float* u, const float* w3, const wl_grid* g, void* st) { GRID_ARG(g); return wl::metrics_helicity(out, u, w3, G, wl_stream(st)); }
+int wl_flow_stats(const float* u, const wl_grid* g, const float* U, double* out, void* scratch, void* st) {
+  GRID_ARG(g); WL_CHECK(out, "wl_flow_stats: null result"); WL_TRY(wl_ctx_ensure());
+  const RedWs ws = wl_red_ws(scratch ? scratch : wl_ctx().red);
+  WL_TRY(wl::metrics_stats_dev(u, G, U, ws, wl_stream(st)));
+  float mx; WL_TRY(wl::read_results(ws, out, 2, &mx, 1, wl_stream(st)));
+  out[2] = (double)mx;
+  return 0;
+}
 int wl_scale_u(float* u, const wl_grid* g, float s, void* st) { GRID_ARG(g); return wl::scale_u(u, G, s, wl_stream(st)); }
 int wl_div(float* z, const float* u, const wl_grid* g, void* st) { GRID_ARG(g); return wl::div(z, u, G, wl_stream(st)); }
 int wl_project(float* u, const float* L, const float* x, const wl_grid* g, void* st) { GRID_ARG(g); return wl::project(u, L, x, G, wl_stream(st)); }

@@ -258,6 +258,12 @@ int conv_diff_z(float* f, const float* u_adv, const float* u0, const float* mu0,
 int bdim(float* u, const float* u0, float* f, const float* V, const float* mu0, const float* mu1, const GridX& g, float dt, float pre, float post, hipStream_t s);
 int accelerate(float* r, const GridX& g, const float* a, hipStream_t s);
 int sgs(float* f, float* sigma, const float* u, const GridX& g, float Cs, float Delta, hipStream_t s);   // sgs! with the Smagorinsky–Lilly νₜ (wl_sgs.hip): 3-D single domain, else WL_EINVAL
+// flow diagnostics of src/Metrics.jl:27-109 (wl_metrics.hip): single-domain grids only, ω-family and λ₂ 3-D only, else WL_EINVAL before any launch
+int metrics_fields(const float* u, const GridX& g, const float* U, float* ke, float* w3, float* wmag, float* l2, hipStream_t s);   // one launch; null outputs are skipped
+int metrics_omega_theta(float* out, const float* u, const GridX& g, const float* z, const float* c, hipStream_t s);
+int metrics_curl(float* out, const float* u, const GridX& g, int i, hipStream_t s);                                                   // i = 1..3 (2-D: 3)
+int metrics_helicity(float* out, const float* u, const float* w3, const GridX& g, hipStream_t s);
+int metrics_stats_dev(const float* u, const GridX& g, const float* U, const RedWs& ws, hipStream_t s);   // Σke, Σ½|ω|² -> ws.res_d[0..1], max|ω| -> ws.res_f[0]; two launches
 int bc_vec_fn(float* a, const float* Ub, const GridX& g, int saveexit, unsigned per, hipStream_t s);
 int add_field(float* r, const float* gfield, size_t n, hipStream_t s);
 int meanflow_update(float* P, float* U, float* UU, const float* p, const float* u, const GridX& g, float e, hipStream_t s);

@@ -1163,5 +1163,22 @@ int wl_sim_pressure_force_bodyset(wl_sim* s, const float* x0, const wl_bodyset* 
 int wl_sim_viscous_force_bodyset(wl_sim* s, const float* x0, const wl_bodyset* set, double* out, void* st) { return sim_force_bodyset(1, s, x0, set, out, st); }
 int wl_sim_measure_sphere(wl_sim* s, const float* c, float R, float eps, void* st) { const wl_body b = sphere_body(c, R); return wl_sim_measure_body(s, &b, eps, st); }
 int wl_sim_pressure_force_sphere(wl_sim* s, const float* c, float R, double* out, void* st) { const wl_body b = sphere_body(c, R); return wl_sim_pressure_force_body(s, &b, out, st); }
+// flow diagnostics on the handle's current velocity (wl_metrics.hip): reads u, writes the caller's outputs and the library's reduction workspace — nothing of the step
+int wl_sim_flow_stats(wl_sim* s, const float* U, double* out, void* st) {
+  WL_CHECK(s && out, "wl_sim_flow_stats: null handle or result");
+  if (s->comm) { wl_set_error("wl_sim_flow_stats: z-slab handles are not supported (single domain only)"); return WL_EINVAL; }
+  WL_TRY(s->settle(wl_stream(st))); WL_TRY(wl_ctx_ensure());
+  const RedWs ws = wl_red_ws(wl_ctx().red);          // the library's workspace, not the solver's: the handle's state is left alone
+  WL_TRY(wl::metrics_stats_dev(s->u, s->G, U, ws, wl_stream(st)));
+  float mx; WL_TRY(wl::read_results(ws, out, 2, &mx, 1, wl_stream(st)));
+  out[2] = (double)mx;
+  return 0;
+}
+int wl_sim_flow_fields(wl_sim* s, const float* U, float* ke, float* w3, float* wmag, float* l2, void* st) {
+  WL_CHECK(s, "wl_sim_flow_fields: null handle");
+  if (s->comm) { wl_set_error("wl_sim_flow_fields: z-slab handles are not supported (single domain only)"); return WL_EINVAL; }
+  WL_TRY(s->settle(wl_stream(st)));
+  return wl::metrics_fields(s->u, s->G, U, ke, w3, wmag, l2, wl_stream(st));
+}
 int wl_sim_viscous_force_sphere(wl_sim* s, const float* c, float R, double* out, void* st) { const wl_body b = sphere_body(c, R); return wl_sim_viscous_force_body(s, &b, out, st); }
 }  // extern "C"

@@ -379,6 +379,28 @@ function update!(m::WaterLily.MeanFlow{Float32,<:HA}, flow::AbstractFlow)
     push!(m.t, m.t[end] + dt)
 end
 
+# flow diagnostics (src/Metrics.jl:27-109).  The reference's forms are per-index functions inside a user's `@inside σ[I] = λ₂(I,u)`: a
+# closure handed to @loop cannot be intercepted (on a HipArray it runs through the CPU staging of get_backend).  Whole-field methods
+# instead, one library call each — `λ₂!(sim.flow.σ, sim.flow.u)` is `@inside sim.flow.σ[I] = WaterLily.λ₂(I,sim.flow.u)`; only inside
+# cells of σ are written.
+nullf() = Ptr{Cfloat}(C_NULL)
+ke!(σ::HA, u::HA; U=nothing) = (chk(ccall((:wl_ke, libwlhip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Ref{WlGrid}, Ptr{Cfloat}, Ptr{Cvoid}),
+                                          σ.ptr, u.ptr, vgrid(u), U === nothing ? nullf() : Cfloat[pad3(U)...], C_NULL)); σ)                      # :33-35
+curl!(σ::HA, u::HA, i) = (chk(ccall((:wl_curl, libwlhip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Ref{WlGrid}, Cint, Ptr{Cvoid}), σ.ptr, u.ptr, vgrid(u), Cint(i), C_NULL)); σ)   # :68
+ω!(w::HA, u::HA) = (chk(ccall((:wl_omega, libwlhip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Ref{WlGrid}, Ptr{Cvoid}), w.ptr, u.ptr, vgrid(u), C_NULL)); w)                     # :74, w: (Ng...,3)
+ω_mag!(σ::HA, u::HA) = (chk(ccall((:wl_omega_mag, libwlhip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Ref{WlGrid}, Ptr{Cvoid}), σ.ptr, u.ptr, vgrid(u), C_NULL)); σ)             # :80
+ω_θ!(σ::HA, u::HA, z, center) = (chk(ccall((:wl_omega_theta, libwlhip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Ref{WlGrid}, Ref{NTuple{3,Cfloat}}, Ref{NTuple{3,Cfloat}}, Ptr{Cvoid}),
+                                           σ.ptr, u.ptr, vgrid(u), Ref(pad3(z)), Ref(pad3(center)), C_NULL)); σ)                                  # :87-91
+λ₂!(σ::HA, u::HA) = (chk(ccall((:wl_lambda2, libwlhip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Ref{WlGrid}, Ptr{Cvoid}), σ.ptr, u.ptr, vgrid(u), C_NULL)); σ)                  # :54-58
+helicity!(σ::HA, u::HA, ω::HA) = (chk(ccall((:wl_helicity, libwlhip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ref{WlGrid}, Ptr{Cvoid}), σ.ptr, u.ptr, ω.ptr, vgrid(u), C_NULL)); σ)   # :99-109
+# (Σ_inside ke(I,u,U), Σ_inside ½|ω|², max_inside |ω|): the kinetic-energy / enstrophy history of a run without u leaving the device
+function flow_stats(u::HA; U=nothing)
+    out = zeros(Cdouble, 3)
+    chk(ccall((:wl_flow_stats, libwlhip), Cint, (Ptr{Cfloat}, Ref{WlGrid}, Ptr{Cfloat}, Ptr{Cdouble}, Ptr{Cvoid}, Ptr{Cvoid}),
+              u.ptr, vgrid(u), U === nothing ? nullf() : Cfloat[pad3(U)...], out, C_NULL, C_NULL))
+    (out[1], out[2], out[3])
+end
+
 # ---- bodies ---------------------------------------------------------------------------------------------------------------------------
 measure!(::HFlow, ::NoBody; kwargs...) = nothing                 # src/Body.jl:83 (resolves the ambiguity with the generic method below)
 # Any AbstractBody whose `measure` is a Julia closure (AutoBody, SetBody, …): the reference's own measure! (src/Body.jl:28-51) runs on

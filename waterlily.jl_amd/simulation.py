@@ -106,6 +106,30 @@ def viscous_moment(x0, a, body):
     return np.array(out[: a.D])
 
 
+METRICS = ("ke", "curl", "omega", "omega_mag", "omega_theta", "lambda2")
+
+
+def _metric_leaf(u, sigma, name, out, **kw):
+    """one diagnostic field of the device velocity array `u` through the leaf functions of metrics.py"""
+    from . import metrics as m
+    from .core import jl_zeros
+    if name not in METRICS:
+        raise ValueError(f"unknown metric {name!r}: one of {METRICS}")
+    Ng = tuple(u.shape[:-1])
+    if isinstance(out, str):
+        assert out == "sigma" and name != "omega", "out='sigma' names the scalar scratch array flow.σ"
+        out = sigma
+    if out is None:
+        out = jl_zeros(Ng + (3,) if name == "omega" else Ng)
+    if name == "ke":
+        return m.ke_(out, u, kw.get("U"))
+    if name == "curl":
+        return m.curl_(out, u, kw.get("i", 3))
+    if name == "omega_theta":
+        return m.omega_theta_(out, u, kw["z"], kw["center"])
+    return {"omega": m.omega_, "omega_mag": m.omega_mag_, "lambda2": m.lambda2_}[name](out, u)
+
+
 class Simulation:
     """Simulation(dims,uBC,L;U,Δt,ν,ϵ,perdir,exitBC,λ,body,T) over leaf operations (reference orchestration)."""
 
@@ -144,6 +168,15 @@ class Simulation:
         if self.body is not None:
             measure_(self.flow, self.body, eps=self.eps)
         self.pois.update_()
+
+    def flow_stats(self, U=None):
+        """(Σke, Σ½|ω|², max|ω|) of flow.u over inside   src/Metrics.jl:33-35,74,80"""
+        from .metrics import flow_stats
+        return flow_stats(self.flow.u, U)
+
+    def metric(self, name, out=None, **kw):
+        """`@inside out[I] = <name>(I,flow.u)` — see FusedSimulation.metric; out="sigma" writes into flow.σ"""
+        return _metric_leaf(self.flow.u, self.flow.sigma, name, out, **kw)
 
     def pressure_force(self):
         return pressure_force(self.flow, self.body)
@@ -429,6 +462,52 @@ class FusedSimulation:
     def total_force_sphere(self, center, R):
         """total_force(sim) = pressure_force + viscous_force   src/Metrics.jl:156-161"""
         return self.pressure_force_sphere(center, R) + self.viscous_force_sphere(center, R)
+
+    def _view(self, name):
+        """the handle's array `name` (its CURRENT role holder) as a device array — valid until the next step rotates the roles"""
+        import torch
+        shape = self._shape(name)
+        p = lib().wl_sim_field(self._h, name.encode())
+        if not p:
+            raise KeyError(name)
+        n = int(np.prod(shape))
+
+        class _Mem:      # __cuda_array_interface__ of memory the handle owns
+            __cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (int(p), False), "version": 2}
+        t = torch.as_tensor(_Mem(), device=core.device())
+        return t.view(tuple(reversed(shape))).permute(*reversed(range(len(shape))))
+
+    def flow_stats(self, U=None):
+        """(Σ_inside ke(I,u,U), Σ_inside ½|ω|², max_inside |ω|) of the current velocity: the kinetic-energy and enstrophy read-out of a
+        run without u leaving the device (src/Metrics.jl:33-35,74,80; 2-D: ω = curl(3,I,u)).  Does not touch the step."""
+        out = (C.c_double * 3)()
+        check(lib().wl_sim_flow_stats(self._h, _x0(U, self.D), out, stream()))
+        return out[0], out[1], out[2]
+
+    def metric(self, name, out=None, **kw):
+        """`@inside out[I] = <name>(I,flow.u)` on the device, name ∈ "ke" (U=…), "curl" (i=…), "omega", "omega_mag", "omega_theta" (z=…, center=…),
+        "lambda2".  out: a device array, None (a new one) or "sigma" (the handle's σ, the reference's scratch).  Returns the device array."""
+        if name not in METRICS:
+            raise ValueError(f"unknown metric {name!r}: one of {METRICS}")
+        if isinstance(out, str):
+            assert out == "sigma" and name != "omega", "out='sigma' names the scalar scratch array flow.σ"
+            out = self._view("sigma")
+        if out is None:
+            out = core.jl_zeros(self.Ng + (3,) if name == "omega" else self.Ng)
+        L = lib()
+        if name in ("ke", "omega", "omega_mag", "lambda2"):
+            k = {"ke": 0, "omega": 1, "omega_mag": 2, "lambda2": 3}[name]
+            args = [ptr(out) if q == k else None for q in range(4)]
+            check(L.wl_sim_flow_fields(self._h, _x0(kw.get("U"), self.D), *args, stream()))
+            return out
+        g = wl_grid()
+        check(L.wl_sim_grid(self._h, C.byref(g)))
+        u = L.wl_sim_field(self._h, b"u")
+        if name == "curl":
+            check(L.wl_curl(ptr(out), u, C.byref(g), int(kw.get("i", 3)), stream()))
+        else:
+            check(L.wl_omega_theta(ptr(out), u, C.byref(g), _x0(kw["z"], 3), _x0(kw["center"], 3), stream()))
+        return out
 
     def sync(self):
         check(lib().wl_stream_sync(stream()))
