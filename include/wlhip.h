@@ -11,7 +11,15 @@
  *    arrays (scalar (Ng...), vector (Ng...,D), tensor (Ng...,D,D)), so `pointer(a)` is passed with no copy.
  *  - All pointers are DEVICE pointers unless named host_*.  Element type: Float32.
  *  - Every call is asynchronous on `stream` (a hipStream_t passed as void*; NULL = default stream)
- *    unless it returns a host scalar, in which case it synchronises that stream.
+ *    unless it returns a host scalar, in which case it synchronises that stream.  Streams the library opens itself (fork/join
+ *    of plane ranges, the communicator's exchange stream) wait for `stream` and are joined back into it before the call returns.
+ *  - Handle creation (wl_mg_create, wl_sim_create, wl_sim_create_on, wl_sim_create_slab, the communicator constructors) takes no
+ *    stream: it works on the DEFAULT stream and returns finished (synchronised).  It reads the caller's L (= μ₀) there, so the
+ *    caller must have synchronised whatever produced the arrays it passes in before it creates the handle.
+ *  - A handle's calls may move from one stream to another; the caller orders the two streams (an event, or a synchronisation),
+ *    as for any other work on the handle's arrays.
+ *  - One host thread at a time: the read-back record, the default reduction workspace and the fork/join events are process-wide.
+ *    Driving the library from several host threads at once is not supported, whatever streams and handles the threads use.
  *  - Return value: 0 = ok; >0 = hipError_t; <0 = library error (WL_E*).  wl_last_error_string() gives text.
  *    No exception crosses this boundary.
  *  - Aliasing pois.x≡flow.p, pois.L≡flow.μ₀, pois.z≡flow.σ (src/WaterLily.jl:97) is allowed everywhere.

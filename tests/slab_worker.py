@@ -2,9 +2,11 @@
 mode cpu_halo : gloo + HOST buffers — exercises the library's halo/all-gather pointer arithmetic and the transport (no GPU).
 mode gpu_sim  : gloo + the one GPU of the box — P slab ranks against the single-domain FusedSimulation.
 """
+import contextlib
 import ctypes as C
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -113,18 +115,39 @@ def main():
             print("smoother kinds per level (slab run):", kinds, flush=True)
         if dims[0] >= 64 and dims[1] >= 32 and dims[2] // size >= 8:
             assert kinds[0] == 2, kinds      # the blocked pair kernels run on the distributed finest level
+        # WL_SLAB_SIDE_STREAM=1: after the first step the ranks (and rank 0's single-domain run) work on a non-blocking side stream, every step behind a
+        # delay, with the default stream blocked (tests/stream_harness.py): the communicator's own stream and its ev_ready / ev_done under a caller's stream
+        side = os.environ.get("WL_SLAB_SIDE_STREAM") == "1"
+        S, sp, ctx = None, None, contextlib.nullcontext()
         for s in range(steps):
-            sim.mom_step_()
-            u = sim.gather_field("u", dist)
-            p = sim.gather_field("p", dist)
+            if side and s == 1:
+                import stream_harness as sh
+                sh.cycles_per_ms()
+                S = sh.pick_streams(1)[0]; sp = C.c_void_p(S.cuda_stream); ctx = torch.cuda.stream(S)      # a stream that does not share the default stream's hardware queue
+                torch.cuda.synchronize()
+                sh.sleep_ms(max(sh.MIN_BLOCK_MS, sh.BLOCK_FACTOR * 1e3 * t_step * (steps - 1) + 3 * sh.MIN_STEP_MS * (steps - 1)))   # default stream blocked
+            t_a = time.perf_counter()
+            with ctx:
+                if S is not None:
+                    sh.sleep_ms(sh.MIN_STEP_MS)
+                sim.mom_step_(sp)
+                u = sim.gather_field("u", dist, sp)
+                p = sim.gather_field("p", dist, sp)
+                if rank == 0:
+                    ref.mom_step_()
+                    ur, pr = ref.field("u"), ref.field("p")
+            t_step = time.perf_counter() - t_a
             if rank == 0:
-                ref.mom_step_()
-                ur, pr = ref.field("u"), ref.field("p")
                 du, dp = np.abs(u - ur).max(), np.abs(p - pr).max()
                 print(f"step {s}: max|du|={du:.3e} max|dp|={dp:.3e} n_slab={sim.pois_n[-2:]} n_ref={ref.pois_n[-2:]} dt={sim.dt[-1]:.6f}/{ref.dt[-1]:.6f}", flush=True)
                 assert sim.pois_n == ref.pois_n
                 assert abs(float(sim.dt[-1]) - float(ref.dt[-1])) <= 1e-6 * float(ref.dt[-1])
                 assert du < 2e-5 and dp < 2e-4, (du, dp)   # only the reductions' association order differs
+        if S is not None:
+            armed = not torch.cuda.default_stream().query()       # the blocker must have outlasted the armed steps
+            torch.cuda.synchronize()
+            assert armed, "not armed: the default-stream blocker ran out before the last step"
+            print(f"rank {rank}: side stream armed", flush=True)
         cnt = C.c_long()
         check(L.wl_sim_counter(sim._h, b"resjac", C.byref(cnt)))
         print(f"rank {rank}: fused projection heads on the slab: {cnt.value}", flush=True)

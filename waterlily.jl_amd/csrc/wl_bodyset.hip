@@ -339,8 +339,8 @@ int wl_bodyset_measure_points(const wl_bodyset* set, int D, const float* hx, int
   WL_TRY(wl_ctx_ensure());
   hipStream_t q = wl_stream(st);
   const size_t nx = (size_t)npts * D;
-  float* buf = nullptr;
-  WL_HIP(hipMalloc((void**)&buf, sizeof(float) * (2 * nx + nx + npts)));
+  float* buf = (float*)wl_scratch(sizeof(float) * (2 * nx + nx + npts));   // (no allocation or free per call: hipFree would wait for every stream of the device)
+  if (!buf) return (int)hipErrorOutOfMemory;
   float *dx = buf, *dn = buf + nx, *dv = buf + 2 * nx, *dd = buf + 3 * nx;
   int rc = 0;
   auto run = [&]() -> int {
@@ -354,7 +354,6 @@ int wl_bodyset_measure_points(const wl_bodyset* set, int D, const float* hx, int
     return 0;
   };
   rc = run();
-  (void)hipFree(buf);
   return rc;
 }
 int wl_measure_bodyset(float* sigma, float* mu0, float* mu1, float* V, const wl_grid* g, const wl_bodyset* set, float eps, int exitBC, uint32_t perdir_mask, void* st) {

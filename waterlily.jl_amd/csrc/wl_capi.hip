@@ -28,6 +28,16 @@ int wl_ctx_ensure() {
   return 0;
 }
 
+void* wl_scratch(size_t bytes) {
+  static void* buf = nullptr; static size_t cap = 0;
+  if (bytes <= cap) return buf;
+  if (buf) { (void)hipFree(buf); buf = nullptr; cap = 0; }
+  const size_t want = bytes < 4096 ? 4096 : bytes;
+  if (hipMalloc(&buf, want) != hipSuccess) { buf = nullptr; wl_set_error("hipMalloc failed for the scratch buffer"); return nullptr; }
+  cap = want;
+  return buf;
+}
+
 long g_wl_launches = 0;
 // two auxiliary streams for launches that are independent of each other (plane ranges of a level with a body): fork/join with events
 namespace wl {

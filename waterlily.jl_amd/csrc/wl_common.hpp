@@ -189,6 +189,10 @@ struct WlCtx {
 };
 WlCtx& wl_ctx();
 int wl_ctx_ensure();
+// Process-wide device scratch for calls that need a small temporary: grow-only, so that a call on a caller's stream neither allocates nor frees once it
+// has run at its size (hipFree waits for the whole device, the default stream included).  One host thread at a time (wlhip.h, Conventions); the caller has
+// synchronised its stream before it returns, so the next user finds the buffer idle.  nullptr: allocation failed (wl_set_error done).
+void* wl_scratch(size_t bytes);
 
 // ---- measurement hooks: event pairs on the launch stream (see wlhip.h WL_PROF_*) ----------------------
 struct WlProf {

@@ -1423,14 +1423,13 @@ int check_const_L(const float* L, const GridX& g, ConstL* out, int* dev_flag, hi
 // planes [za,zb] (inclusive, local indices) outside which every coefficient of L follows the constant pattern with constants c;
 // za > zb: none deviates.  Host-synchronising (update! time only).  Single domain, 3-D.
 int const_plane_range(const float* L, const GridX& g, const float* c, int* za, int* zb, hipStream_t s) {
-  unsigned char* d = nullptr;
-  WL_HIP(hipMalloc((void**)&d, (size_t)g.nz));
+  unsigned char* d = (unsigned char*)wl_scratch((size_t)g.nz);
+  if (!d) return (int)hipErrorOutOfMemory;
   WL_HIP(hipMemsetAsync(d, 0, (size_t)g.nz, s));
   DSEL(g.D, k_plane_bad, wl_plane_grid(g, g.nz), dim3(WL_BLOCK), 0, s, g, L, c[0], c[1], c[2], d);
   std::vector<unsigned char> h((size_t)g.nz);
   WL_HIP(hipMemcpyAsync(h.data(), d, h.size(), hipMemcpyDeviceToHost, s));
   WL_HIP(hipStreamSynchronize(s));
-  (void)hipFree(d);
   *za = g.nz; *zb = -1;
   for (int k = 0; k < g.nz; k++) if (h[(size_t)k]) { if (k < *za) *za = k; if (k > *zb) *zb = k; }
   return 0;

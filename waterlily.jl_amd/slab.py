@@ -40,12 +40,14 @@ class CallbackComm:
         self.size = dist.get_world_size() if size is None else size
         L = lib()
         if host_buffers:
-            self._out = lambda dst, src, n: C.memmove(dst.ctypes.data, src, n)
-            self._in = lambda dst, src, n: C.memmove(dst, src.ctypes.data, n)
+            self._out = lambda dst, src, n, st: C.memmove(dst.ctypes.data, src, n)
+            self._in = lambda dst, src, n, st: C.memmove(dst, src.ctypes.data, n)
             self._sync = lambda st: None
         else:
-            self._out = lambda dst, src, n: check(L.wl_d2h(dst.ctypes.data_as(C.c_void_p), src, n, None))
-            self._in = lambda dst, src, n: (check(L.wl_h2d(dst, src.ctypes.data_as(C.c_void_p), n, None)), check(L.wl_stream_sync(None)))
+            # the copies run on the stream the library hands to the callback (never on the default stream: a caller on a non-blocking stream
+            # must not be serialised behind whatever the default stream holds)
+            self._out = lambda dst, src, n, st: check(L.wl_d2h(dst.ctypes.data_as(C.c_void_p), src, n, st))
+            self._in = lambda dst, src, n, st: (check(L.wl_h2d(dst, src.ctypes.data_as(C.c_void_p), n, st)), check(L.wl_stream_sync(st)))
             self._sync = lambda st: check(L.wl_stream_sync(st))
         self._sr = SENDRECV_FN(self._sendrecv)
         self._ag = ALLGATHER_FN(self._allgather)
@@ -62,10 +64,10 @@ class CallbackComm:
             # ghosts), tag 1: planes travelling up — with two ranks both neighbours are the same process and the tags keep the two apart
             lo, hi = (self.rank - 1) % self.size, (self.rank + 1) % self.size
             if slo:
-                b = np.empty(nbytes, dtype=np.uint8); self._out(b, slo, nbytes); t = torch.from_numpy(b); keep.append(t)
+                b = np.empty(nbytes, dtype=np.uint8); self._out(b, slo, nbytes, stream); t = torch.from_numpy(b); keep.append(t)
                 reqs.append(dist.isend(t, lo, group=self.group, tag=0))
             if shi:
-                b = np.empty(nbytes, dtype=np.uint8); self._out(b, shi, nbytes); t = torch.from_numpy(b); keep.append(t)
+                b = np.empty(nbytes, dtype=np.uint8); self._out(b, shi, nbytes, stream); t = torch.from_numpy(b); keep.append(t)
                 reqs.append(dist.isend(t, hi, group=self.group, tag=1))
             rl = rh = None
             if rlo:
@@ -75,9 +77,9 @@ class CallbackComm:
             for r in reqs:
                 r.wait()
             if rl is not None:
-                self._in(rlo, rl.numpy(), nbytes)
+                self._in(rlo, rl.numpy(), nbytes, stream)
             if rh is not None:
-                self._in(rhi, rh.numpy(), nbytes)
+                self._in(rhi, rh.numpy(), nbytes, stream)
             return 0
         except Exception as e:  # never let an exception cross the C boundary
             print("halo callback error:", repr(e), flush=True)
@@ -87,11 +89,11 @@ class CallbackComm:
         try:
             torch, dist = self.torch, self.dist
             self._sync(stream)
-            b = np.empty(nbytes, dtype=np.uint8); self._out(b, send, nbytes)
+            b = np.empty(nbytes, dtype=np.uint8); self._out(b, send, nbytes, stream)
             outs = [torch.empty(nbytes, dtype=torch.uint8) for _ in range(self.size)]
             dist.all_gather(outs, torch.from_numpy(b), group=self.group)
             for r, t in enumerate(outs):
-                self._in(recv + r * nbytes, t.numpy(), nbytes)
+                self._in(recv + r * nbytes, t.numpy(), nbytes, stream)
             return 0
         except Exception as e:
             print("allgather callback error:", repr(e), flush=True)
@@ -187,8 +189,8 @@ class SlabSimulation:
                 pass
             self._h = None
 
-    def mom_step_(self):
-        check(lib().wl_sim_mom_step(self._h, None))
+    def mom_step_(self, stream=None):
+        check(lib().wl_sim_mom_step(self._h, stream))
 
     def measure_sphere_(self, center, R, eps=1.0):
         """measure!(sim) for AutoBody(|x-c|-R) in GLOBAL coordinates: closed form on device + update!(pois)"""
@@ -248,19 +250,19 @@ class SlabSimulation:
         k = lib().wl_mg_history(lib().wl_sim_pois(self._h), out, 65536)
         return [int(v) for v in out[:k]]
 
-    def local_field(self, name):
+    def local_field(self, name, stream=None):
         """this rank's slab (all local planes incl. ghosts), Fortran order"""
         g = self.grid
         nc = {"p": (), "sigma": ()}.get(name, (3,))
         out = np.empty((g.nx, g.ny, g.nz) + nc, dtype=np.float32, order="F")
-        check(lib().wl_d2h(out.ctypes.data_as(C.c_void_p), lib().wl_sim_field(self._h, name.encode()), out.nbytes, None))
+        check(lib().wl_d2h(out.ctypes.data_as(C.c_void_p), lib().wl_sim_field(self._h, name.encode()), out.nbytes, stream))
         return out
 
-    def gather_field(self, name, dist):
+    def gather_field(self, name, dist, stream=None):
         """assemble the global ghosted array on every rank from the owned planes (+ the physical z-ghost planes)"""
         import torch
         g = self.grid
-        loc = self.local_field(name)
+        loc = self.local_field(name, stream)
         lo = g.k0 - (1 if g.gk + g.k0 == 1 else 0)
         hi = g.k1 + (1 if g.gk + g.k1 == g.gnz - 1 else 0)
         mine = np.ascontiguousarray(loc[:, :, lo:hi])
