@@ -36,7 +36,14 @@ int wl_placement_scores(double* out, int cap);
  * "tailfuse" = projections whose velocity update (u −= L∇x, BC!) was evaluated by the corrector's conv_diff! loader instead of a tail launch,
  * "tailfuse_min" = no count: the size gate of that path in force on this handle (interior cells; option "tailfuse_min"),
  * "xdefer" = what the finest level's last smooth! decided: 1 the V-cycle's x += ω·x_c↓ was applied by smoother kernel B, 0 by kernel A, −1 none yet
- * (decides which bytes bench.py books to kernels A and B) */
+ * (decides which bytes bench.py books to kernels A and B),
+ * flows with a body — which body-aware path ran: "hybrid" = predict/correct calls that took the body-aware conv_diff!+BDIM! (two per step where live),
+ * "body_tile" = tiled far-range launches of that path (PROCESS-wide, like the option: read it as a difference), "mask_valid" = 1 while the masks of the last
+ * measure!/update! are in force (0 after wl_sim_field handed out V, mu0 or mu1), "part" / "part_za" / "part_zb" = the finest level runs the z-split smoother /
+ * the planes whose coefficients are off the constant pattern;
+ * the mask census of the last refresh, per (plane, workgroup of 256 in-plane cells): "mask_near", "mask_needf_only" (f kept for a neighbour, not near),
+ * "mask_m0var_only" (only μ₀ off the wall pattern), "mask_clean_in_box" (inside the near bounding box, not near), "dirty_z0" / "dirty_z1" (first / last plane
+ * with any mark; z1 < z0: none), "near_b0" / "near_b1" / "near_k0" / "near_k1" (the bounding box; b1 < b0: empty) */
 int wl_sim_counter(wl_sim* s, const char* name, long* out);
 
 #ifdef __cplusplus

@@ -293,8 +293,12 @@ size_t body_mask_bytes(const GridX& g);
 int conv_diff_bdim_body(float* f, const float* u_adv, float* Phi, const float* u0, const float* mu0, float* u_out, const GridX& g, float nu, unsigned per, int scheme,
                         float dt, float pre, float post, const unsigned char* near, const unsigned char* needf, const unsigned char* m0var, int nbm, int store_all, hipStream_t s,
                         int dz0 = 0, int dz1 = -1);   // dz0..dz1: body_masks_planes (planes outside run the tiled NoBody kernel)
-int body_masks_planes(const unsigned char* near, const unsigned char* needf, const unsigned char* m0var, const GridX& g, int* dz, hipStream_t s);
+// what the masks held at the last refresh, counted per (plane, in-plane workgroup) from the host copy body_masks_planes makes anyway (wl_sim_counter "mask_*")
+struct MaskCensus { long near = 0, needf_only = 0, m0var_only = 0, clean_in_box = 0; };   // needf && !near / m0var && !near && !needf / inside `box`, near == 0
+int body_masks_planes(const unsigned char* near, const unsigned char* needf, const unsigned char* m0var, const GridX& g, int* dz, hipStream_t s,
+                      const int* box = nullptr, MaskCensus* census = nullptr);
 void conv_body_tile_enable(int on);
+long conv_body_tile_launches();      // tiled far-range launches conv_diff_bdim_body has made in this process
 int body_masks_nbm(const GridX& g);
 int body_masks(unsigned char* near, unsigned char* needf, unsigned char* m0var, const float* V, const float* mu1, const float* mu0, const GridX& g, hipStream_t s);
 int bdim_near(float* uout, const float* uin, const float* u0, float* f, const float* V, const float* mu0, const float* mu1, const GridX& g, float dt, float pre, float post,

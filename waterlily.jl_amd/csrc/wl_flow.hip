@@ -784,6 +784,8 @@ int conv_diff_bdim(float* f, const float* u_adv, float* Phi, const float* u0, co
 // those planes run the LDS-tiled kernel (wl_convt.hip) in its NoBody form, the planes dz0..dz1 this file's gather kernel (FUSE=2).
 int g_body_tile = 1;
 void conv_body_tile_enable(int on) { g_body_tile = on; }
+static long g_body_tile_launches = 0;
+long conv_body_tile_launches() { return g_body_tile_launches; }
 int conv_diff_bdim_body(float* f, const float* u_adv, float* Phi, const float* u0, const float* mu0, float* u_out, const GridX& g, float nu, unsigned per, int scheme,
                         float dt, float pre, float post, const unsigned char* near, const unsigned char* needf, const unsigned char* m0var, int nbm, int store_all, hipStream_t s,
                         int dz0, int dz1) {
@@ -796,15 +798,17 @@ int conv_diff_bdim_body(float* f, const float* u_adv, float* Phi, const float* u
     const int nfar = (na - g.k0) + (g.k1 - nb);
     if (nfar > 0 && nb > na && wl::conv_tile_ok(g, per, 2 * nfar)) {                  // (half the NoBody size gate: the launch replaces a much slower kernel)
       BdimArgs bt{u0, mu0, u_out, dt, pre, post, (post != 1.f) ? 1 : 0, 1, {1.f, 1.f, 1.f}};
-      if (na > g.k0) WL_TRY(wl::conv_tile(u_adv, g, nu, scheme, g.k0, na, &bt, s));
-      if (g.k1 > nb) WL_TRY(wl::conv_tile(u_adv, g, nu, scheme, nb, g.k1, &bt, s));
-      return conv_diff_launch<3>(f, u_adv, Phi, g, nu, per, scheme, s, &bd, na, nb);
+      if (na > g.k0) { WL_TRY(wl::conv_tile(u_adv, g, nu, scheme, g.k0, na, &bt, s)); g_body_tile_launches++; }
+      if (g.k1 > nb) { WL_TRY(wl::conv_tile(u_adv, g, nu, scheme, nb, g.k1, &bt, s)); g_body_tile_launches++; }
+      // a gather range that starts (ends) at the first (last) owned plane takes the ghost plane beyond it along, as the launch over the whole domain does: a body
+      // cut by the z wall with V ≠ 0 has near workgroups there (BC!(V) copies the tangential components), and μddn of the first owned plane reads that plane's f
+      return conv_diff_launch<3>(f, u_adv, Phi, g, nu, per, scheme, s, &bd, na == g.k0 ? -(1 << 30) : na, nb == g.k1 ? 1 << 30 : nb);
     }
   }
   return g.D == 3 ? conv_diff_launch<3>(f, u_adv, Phi, g, nu, per, scheme, s, &bd) : conv_diff_launch<2>(f, u_adv, Phi, g, nu, per, scheme, s, &bd);
 }
 // first / last plane (inclusive) on which any workgroup is near the body, keeps f or loads μ₀; host-synchronising (measure!/update! time only)
-int body_masks_planes(const unsigned char* near, const unsigned char* needf, const unsigned char* m0var, const GridX& g, int* dz, hipStream_t s) {
+int body_masks_planes(const unsigned char* near, const unsigned char* needf, const unsigned char* m0var, const GridX& g, int* dz, hipStream_t s, const int* box, MaskCensus* census) {
   const int nbm = body_masks_nbm(g);
   const size_t n = (size_t)nbm * g.nz;
   std::vector<unsigned char> h(3 * n);
@@ -817,6 +821,16 @@ int body_masks_planes(const unsigned char* near, const unsigned char* needf, con
     bool any = false;
     for (int b = 0; b < nbm && !any; b++) any = h[(size_t)k * nbm + b] || h[n + (size_t)k * nbm + b] || h[2 * n + (size_t)k * nbm + b];
     if (any) { if (k < dz[0]) dz[0] = k; if (k > dz[1]) dz[1] = k; }
+  }
+  if (census) {
+    *census = MaskCensus{};
+    for (int k = 0; k < g.nz; k++) for (int b = 0; b < nbm; b++) {
+      const size_t q = (size_t)k * nbm + b;
+      if (h[q]) census->near++;
+      else if (h[n + q]) census->needf_only++;
+      else if (h[2 * n + q]) census->m0var_only++;
+      if (box && !h[q] && b >= box[0] && b <= box[1] && k >= box[2] && k <= box[3]) census->clean_in_box++;
+    }
   }
   return 0;
 }

@@ -365,6 +365,8 @@ struct wl_sim {
   int near_box[4] = {0, -1, 0, -1};   // {b0,b1,k0,k1}: bounding box of the near workgroups
   int dirty_z[2] = {0, -1};           // first / last plane with any near / f-keeping / μ₀-loading workgroup (the other planes are NoBody planes)
   bool use_hybrid = true;
+  long n_hybrid = 0;                  // predict/correct calls that went through conv_bdim_body
+  wl::MaskCensus census;              // what the masks held at the last refresh (read-outs only: wl_sim_counter "mask_*")
   bool hybrid_ok() const { return d.has_body && use_hybrid && mask_valid && mnear && us && !comm && !forcing && !sgs_model && !d.exitBC; }
   int refresh_body_mask(hipStream_t s) {
     if (!d.has_body || !mu1 || !V) return 0;
@@ -373,12 +375,13 @@ struct wl_sim {
     mask_valid = true;
     WL_TRY(wl::body_masks(mnear, mneedf, mm0var, V, mu1, mu0, G, s));
     WL_TRY(wl::body_masks_box(mnear, G, near_box, s));
-    WL_TRY(wl::body_masks_planes(mnear, mneedf, mm0var, G, dirty_z, s));
+    WL_TRY(wl::body_masks_planes(mnear, mneedf, mm0var, G, dirty_z, s, near_box, &census));
     return wl::body_mask(farmask, V, mu1, G, s);
   }
   // conv_diff!(f,uadv) + BDIM! with a body: fused NoBody form far from the body, two-pass BDIM! on the near workgroups only
   int conv_bdim_body(const float* uadv, float* uout, float pre, float post, hipStream_t s) {
     WL_TRY(sync_u(s));
+    n_hybrid++;
     { ProfScope pc(WL_PROF_CONVDIFF, s);
       WL_TRY(wl::conv_diff_bdim_body(f, uadv, sigma, u0, mu0, uout, G, d.nu, d.perdir_mask, d.scheme, dt.back(), pre, post, mnear, mneedf, mm0var, wl::body_masks_nbm(G), store_f ? 1 : 0, s, dirty_z[0], dirty_z[1])); }
     ProfScope pb(WL_PROF_BDIM, s);
@@ -986,6 +989,23 @@ int wl_sim_counter(wl_sim* s, const char* name, long* out) {
   if (n == "tailspec") { *out = s->n_tailspec; return 0; }
   if (n == "tailspec_armed") { *out = s->n_tailspec_armed; return 0; }
   if (n == "xdefer") { *out = s->mg->last_xdefer; return 0; }
+  // which body-aware path ran, and what the masks held at the last refresh (measure!/update!)
+  if (n == "hybrid") { *out = s->n_hybrid; return 0; }
+  if (n == "body_tile") { *out = wl::conv_body_tile_launches(); return 0; }      // (process-wide, like the switch: read it as a difference)
+  if (n == "mask_valid") { *out = s->mask_valid ? 1 : 0; return 0; }
+  if (n == "mask_near") { *out = s->census.near; return 0; }
+  if (n == "mask_needf_only") { *out = s->census.needf_only; return 0; }
+  if (n == "mask_m0var_only") { *out = s->census.m0var_only; return 0; }
+  if (n == "mask_clean_in_box") { *out = s->census.clean_in_box; return 0; }
+  if (n == "dirty_z0") { *out = s->dirty_z[0]; return 0; }
+  if (n == "dirty_z1") { *out = s->dirty_z[1]; return 0; }
+  if (n == "near_b0") { *out = s->near_box[0]; return 0; }
+  if (n == "near_b1") { *out = s->near_box[1]; return 0; }
+  if (n == "near_k0") { *out = s->near_box[2]; return 0; }
+  if (n == "near_k1") { *out = s->near_box[3]; return 0; }
+  if (n == "part") { *out = s->mg->lv[0].part ? 1 : 0; return 0; }                 // the finest level's z-split: decided / planes [za, zb] off the constant pattern
+  if (n == "part_za") { *out = s->mg->lv[0].za; return 0; }
+  if (n == "part_zb") { *out = s->mg->lv[0].zb; return 0; }
   wl_set_error("unknown counter " + n); return WL_EINVAL;
 }
 int wl_sim_set_forcing(wl_sim* s, const float* U1, const float* a0, const float* a1) {
