@@ -167,7 +167,10 @@ int wl_mg_destroy(wl_mg* mg);
 int wl_mg_update(wl_mg* mg, void* stream);
 int wl_mg_nlevels(const wl_mg* mg);
 int wl_mg_level_grid(const wl_mg* mg, int level, wl_grid* out);
-/* name ∈ "L","D","iD","x","eps","r","z" — device pointer of that level's array (tests read pois.levels[k].D etc.) */
+/* name ∈ "L","D","iD","x","eps","r","z" — device pointer of that level's array (tests read pois.levels[k].D etc.).
+ * On the multigrid handle of a simulation composite, whose option "rskip" is on by default, the smoother does not store residuals nobody reads: level 0's "r" is brought up to date by this call
+ * (if the last smooth! skipped its store: one launch on the stream that smooth! ran on, waited for; ask again after every solve), a coarse level's "r" is
+ * unspecified scratch. */
 float* wl_mg_level_field(const wl_mg* mg, int level, const char* name);
 int wl_mg_vcycle(wl_mg* mg, int level, float omega, void* stream);
 int wl_mg_smooth(wl_mg* mg, int level, int it, float omega, void* stream);      /* smooth! = GaussSeidelRB! on one level (:106) */

@@ -32,6 +32,8 @@ int wl_placement_scores(double* out, int cap);
  * "tailspec" = projection tails that ran from inside the solver loop, ahead of the convergence read,
  * "tailspec_armed" = solves the gated tail was queued for (the difference to "tailspec": withheld — the cap was hit, or the fused head's mean shift was due),
  * "pdefer" = projection tails that did not store p = x/Δt (the next fused head divided on load): 2k − 1 for a k-step wl_sim_mom_steps call where the option is live,
+ * "rskip" = finest-level launches of smoother kernel B that did not store the residual (option "rskip": the iteration at which the slot's previous solve stopped),
+ * "rskip_redo" = launches of its r-only form that produced such a residual after all (the loop went on, or wl_mg_level_field / wl_mg_smooth / wl_mg_vcycle asked),
  * "tailwide" = projection tails that ran in the four-cells-per-thread form (two per step where the option is live and the shape allows it),
  * "tailfuse" = projections whose velocity update (u −= L∇x, BC!) was evaluated by the corrector's conv_diff! loader instead of a tail launch,
  * "tailfuse_min" = no count: the size gate of that path in force on this handle (interior cells; option "tailfuse_min"),

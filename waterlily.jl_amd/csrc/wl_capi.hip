@@ -206,7 +206,24 @@ int wl_mg::flush_pending(int l, float w, hipStream_t s) {
   return wl::prolong_increment(fine.r, fine.x, fine.eps, coarse.x, fine.L, fine.D, fine.x_, coarse.x_, w, true, s);
 }
 // GaussSeidelRB!(p;it,ω)                                                                 src/Poisson.jl:141-148
-int wl_mg::smooth(int l, int it, float w, hipStream_t s, bool want_norms, bool* norms_done) {
+// the residual of the finest level that a smooth! with skip_r left unwritten: kernel B again with the same arguments, storing r' only
+int wl_mg::settle_r(hipStream_t s) {
+  if (!r_stale) return 0;
+  Level& p = lv[0];
+  r_stale = false; n_rskip_redo++;
+  return wl::gsrb_fused_B(nullptr, p.r, p.x, p.em, p.rs, p.L, p.x_, r_stale_w, nullptr, 2, 1, p.cl, s, nullptr, wl::B_RONLY);
+}
+// … for a reader that names no stream: behind the launch that skipped the store, on its stream (stream 0 if that stream is gone), and complete on return —
+// whichever stream the caller then reads r on finds it current
+int wl_mg::settle_r_for_reader() {
+  if (!r_stale) return 0;
+  hipStream_t s = r_stale_stream;
+  if (s) { const hipError_t q = hipStreamQuery(s); if (q != hipSuccess && q != hipErrorNotReady) { (void)hipGetLastError(); s = nullptr; } }
+  WL_TRY(settle_r(s));
+  WL_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+int wl_mg::smooth(int l, int it, float w, hipStream_t s, bool want_norms, bool* norms_done, int bout) {
   Level& p = lv[(size_t)l];
   if (norms_done) *norms_done = false;
   const bool fused = it == 4 && use_fused && (wl::gsrb_fused_ok(p.x_, perdir, p.dist) || pair_slab(p));
@@ -312,7 +329,11 @@ int wl_mg::smooth(int l, int it, float w, hipStream_t s, bool want_norms, bool* 
         if (grp) { const int rc2 = comm->group_end(); if (rc == 0) rc = rc2; }
         WL_TRY(rc);
       }
-      { ProfScope pb(l == 0 ? WL_PROF_GS_B : -1, s); WL_TRY(wl::gsrb_fused_B(store_eps ? p.eps : nullptr, p.r, p.x, p.em, p.rs, p.L, p.x_, w, nws, 2, 1, p.cl, s, xdef ? &xd : nullptr)); }
+      // skip_r: r' stays in kernel B's registers (the norms) — p.em and p.rs are left as they are, so settle_r can still produce it
+      const bool xonly = bout == wl::B_XONLY && skip_r && !store_eps && !comm && !p.dist && !p.part && !perdir && wl::gsrb_pair_B_ok(nullptr, p.r, p.x, p.em, p.rs, p.x_, p.cl) &&
+                         (!want_norms || wl::gsrb_pair_B_kernel_norms(p.x_));
+      { ProfScope pb(l == 0 ? WL_PROF_GS_B : -1, s); WL_TRY(wl::gsrb_fused_B(store_eps ? p.eps : nullptr, p.r, p.x, p.em, p.rs, p.L, p.x_, w, nws, 2, 1, p.cl, s, xdef ? &xd : nullptr, xonly ? wl::B_XONLY : wl::B_BOTH)); }
+      if (xonly && l == 0) { r_stale = true; r_stale_w = w; r_stale_stream = s; n_rskip++; }
     } else {
       WL_TRY(halo(p, p.r, 1, s, 2));
       { ProfScope pa(l == 0 ? WL_PROF_GS_A : -1, s); WL_TRY(wl::gsrb_fused_A(p.em, p.r, p.L, p.x_, p.cl, s)); }
@@ -399,7 +420,7 @@ int wl_mg::vcycle(int l, float w, hipStream_t s, bool defer) {                  
     if (to_tail) WL_TRY(tail(l + 1, w, s));                                         // everything below in one launch
     else {
       if (l + 2 < (int)lv.size()) WL_TRY(vcycle(l + 1, w, s, true));                       // its last step may be deferred into the smooth! below
-      WL_TRY(smooth(l + 1, 4, w, s));
+      WL_TRY(smooth(l + 1, 4, w, s, false, nullptr, skip_r ? wl::B_XONLY : wl::B_BOTH));   // only coarse.x is read from here on; the next restrict! overwrites coarse.r
     }
     WL_TRY(halo(coarse, coarse.x, 1, s, pair_slab(fine) ? ((deep_halo && fine.g.k0 >= 5 && fine.g.k1 - fine.g.k0 >= 5 && coarse.g.k0 >= 3 && coarse.g.k1 - coarse.g.k0 >= 3) ? 3 : 2) : 1));   // prolongation reads the coarse cells under my halo planes (deep halo: kernel A starts 5 planes out)
   }
@@ -411,6 +432,8 @@ int wl_mg::vcycle(int l, float w, hipStream_t s, bool defer) {                  
 }
 int wl_mg::solve(double tol, int itmx, int* host_n, double* host_r1, float* host_rinf, hipStream_t s, bool have_residual, const double* pre_r1, const float* pre_rinf) {   // solver! :108-128
   Level& p = lv[0];
+  r_stale = false;   // r is rebuilt from scratch below, or was by the caller
+  const int hit_at = (skip_r && rskip_slot >= 0 && rskip_slot < 2) ? rskip_hist[rskip_slot] : 0;   // the iteration this slot's last solve stopped at: its r' is not stored
   const double r1tol = (tol / 10.0) * (double)wl_ninside_global(p.g);                     // l1n_tol  src/Poisson.jl:194
   const double rinftol = tol;
   {
@@ -438,10 +461,11 @@ int wl_mg::solve(double tol, int itmx, int* host_n, double* host_r1, float* host
   const int check_head = spec_check_head; spec_check_head = 0;
   tail_stood = head_decided = head_due = false;
   while (np < itmx) {
+    WL_TRY(settle_r(s));                                                                   // the loop goes on after a skipped store: r' from the r-only instance
     WL_TRY(vcycle(0, w, s, true));
     bool nd = false;
     norm_slots = 0;
-    WL_TRY(smooth(0, 4, w, s, true, &nd));                                                // fused path: norms come out of kernel B
+    WL_TRY(smooth(0, 4, w, s, true, &nd, np + 1 == hit_at ? wl::B_XONLY : wl::B_BOTH));                                                // fused path: norms come out of kernel B
     if (!nd) { norm_slots = 0; WL_TRY(wl::norms_dev(lv[0].r, p.x_, ws, 2, 1, s)); }       // rnew -> res_d[2], r∞ -> res_f[1]
     WL_TRY(wl::combine_results(comm, ws, s));                                             // (slot 0 becomes P·Σr: not used again)
     const bool spec = (bool)tail && norm_slots == 0 && !comm;
@@ -477,6 +501,7 @@ int wl_mg::solve(double tol, int itmx, int* host_n, double* host_r1, float* host
   WL_TRY(wl::bc_per_scalar(p.x, p.x_, perdir, s));                                        // :126
   WL_TRY(halo(p, p.x, 1, s, x_halo_depth));                                               // projection reads x[I-δz] across the slab face (the next solve's fused head two planes deep)
   n.push_back((int16_t)np);
+  if (rskip_slot >= 0 && rskip_slot < 2 && !head_due) rskip_hist[rskip_slot] = np;         // (a solve the caller discards is nobody's history)
   if (host_n) *host_n = np;
   if (host_r1) *host_r1 = (double)r1;
   if (host_rinf) *host_rinf = rinf;
@@ -688,11 +713,12 @@ int wl_mg_level_grid(const wl_mg* mg, int l, wl_grid* out) { WL_CHECK(l >= 0 && 
 float* wl_mg_level_field(const wl_mg* mg, int l, const char* name) {
   if (l < 0 || l >= (int)mg->lv.size()) return nullptr;
   const wl_mg::Level& v = mg->lv[(size_t)l]; const std::string s(name);
+  if (l == 0 && s == "r" && const_cast<wl_mg*>(mg)->settle_r_for_reader() != 0) return nullptr;   // skip_r: the finest residual is produced when somebody asks for it
   if (s == "L") return v.L; if (s == "D") return v.D; if (s == "iD") return v.iD; if (s == "x") return v.x;
   if (s == "eps") return v.eps; if (s == "r") return v.r; if (s == "z") return v.z;
   return nullptr;
 }
-int wl_mg_smooth(wl_mg* mg, int l, int it, float w, void* st) { WL_CHECK(l >= 0 && l < (int)mg->lv.size(), "level out of range"); return mg->smooth(l, it <= 0 ? 4 : it, w, wl_stream(st)); }
+int wl_mg_smooth(wl_mg* mg, int l, int it, float w, void* st) { WL_CHECK(l >= 0 && l < (int)mg->lv.size(), "level out of range"); if (l == 0) WL_TRY(mg->settle_r(wl_stream(st))); return mg->smooth(l, it <= 0 ? 4 : it, w, wl_stream(st)); }
 int wl_mg_smoother_kind(const wl_mg* mg, int l) {   // 0 one kernel per pass, 1 temporally blocked (one cell per thread), 2 blocked pair kernels (constant coefficients)
   if (l < 0 || l >= (int)mg->lv.size()) return -1;
   const wl_mg::Level& p = mg->lv[(size_t)l];
@@ -703,7 +729,7 @@ int wl_mg_smoother_kind(const wl_mg* mg, int l) {   // 0 one kernel per pass, 1 
 }
 int wl_mg_level_is_const(const wl_mg* mg, int l) { return (l >= 0 && l < (int)mg->lv.size()) ? mg->lv[(size_t)l].cl.on : 0; }
 int wl_mg_set_fused(wl_mg* mg, int on) { mg->use_fused = (on & 1) != 0; mg->store_eps = (on & 2) == 0; wl::gsrb_pair_enable((on & 4) == 0); mg->use_tail = (on & 8) == 0; mg->use_zsplit = (on & 16) == 0; wl::tail_lds_enable((on & 32) == 0); mg->use_xdefer = (on & 64) == 0; mg->overlap_smooth = (on & 128) == 0; return 0; }
-int wl_mg_vcycle(wl_mg* mg, int l, float w, void* st) { WL_CHECK(l >= 0 && l + 1 < (int)mg->lv.size(), "level out of range"); return mg->vcycle(l, w, wl_stream(st), false); }
+int wl_mg_vcycle(wl_mg* mg, int l, float w, void* st) { WL_CHECK(l >= 0 && l + 1 < (int)mg->lv.size(), "level out of range"); if (l == 0) WL_TRY(mg->settle_r(wl_stream(st))); return mg->vcycle(l, w, wl_stream(st), false); }
 int wl_mg_solve(wl_mg* mg, double tol, int itmx, int* n, double* r1, float* rinf, void* st) { return mg->solve(tol, itmx <= 0 ? 32 : itmx, n, r1, rinf, wl_stream(st)); }
 int wl_mg_history(const wl_mg* mg, int16_t* out, int cap) { const int n = (int)mg->n.size(); for (int k = 0; k < n && k < cap; k++) out[k] = mg->n[(size_t)k]; return n; }
 int wl_mg_shift_path(const wl_mg* mg) { return mg->shift_path; }

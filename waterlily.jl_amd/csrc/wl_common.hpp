@@ -360,7 +360,7 @@ int gsrb_fused_A_pro(float* emid, float* rnew, float* x, const float* r, const f
 struct XDefer { const float* xc; GridX gc; float w; };
 bool gsrb_pair_B_ok(const float* eps, const float* rout, const float* x, const float* emid, const float* r, const GridX& g, const ConstL& cl);
 int gsrb_fused_B(float* eps, float* rout, float* x, const float* emid, const float* r, const float* L, const GridX& g, float w,
-                 const RedWs* ws, int slot_d, int slot_f, const ConstL& cl, hipStream_t s, const XDefer* xd = nullptr);   // xd: only when gsrb_pair_B_ok
+                 const RedWs* ws, int slot_d, int slot_f, const ConstL& cl, hipStream_t s, const XDefer* xd = nullptr, int out = 0);   // xd, out ≠ 0 (wl::BOut): only when gsrb_pair_B_ok
 int finalize_sum_max(const RedWs& ws, int nparts, int slot_d, int slot_f, hipStream_t s);
 // pair variant of the blocked smoother for constant-coefficient levels (wl_fused2.hip); chosen inside gsrb_fused_* when eligible
 void gsrb_pair_enable(int on);
@@ -370,8 +370,12 @@ bool gsrb_pair_geom_ok(const GridX& g);
 int gsrb_pair_A(float* emid, const float* r, const GridX& g, const ConstL& cl, hipStream_t s);
 int gsrb_pair_A_pro(float* emid, float* rnew, float* x, const float* r, const float* xc, const GridX& g, const GridX& gc, float w, const ConstL& cl, hipStream_t s,
                     int xk0 = -(1 << 30), int xk1 = 1 << 30);   // [xk0,xk1): planes on which x is updated (default: every output plane)
+// which of increment!'s results kernel B of the pair smoother stores: both (default) | x only — rout is not written, and since the launch leaves its inputs
+// ϵ_mid and r alone, | r only with the same arguments produces rout afterwards, bit for bit (neither loads nor stores x, no norms)
+enum BOut { B_BOTH = 0, B_XONLY = 1, B_RONLY = 2 };
 int gsrb_pair_B(float* eps, float* rout, float* x, const float* emid, const float* r, const GridX& g, float w,
-                const RedWs* ws, int slot_d, int slot_f, const ConstL& cl, hipStream_t s, const XDefer* xd = nullptr);
+                const RedWs* ws, int slot_d, int slot_f, const ConstL& cl, hipStream_t s, const XDefer* xd = nullptr, int out = B_BOTH);
+bool gsrb_pair_B_kernel_norms(const GridX& g);   // a launch with ws takes the norms from registers (else: from the stored rout — B_XONLY is refused)
 int restrict_(float* a, const GridX& gc, const float* b, const GridX& gf, hipStream_t s);
 int prolongate(float* a, const GridX& gf, const float* b, const GridX& gc, hipStream_t s);
 int prolong_increment(float* r, float* x, float* eps, const float* xc, const float* L, const float* D, const GridX& gf, const GridX& gc, float w, bool write_eps, hipStream_t s);

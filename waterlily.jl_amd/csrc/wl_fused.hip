@@ -346,8 +346,9 @@ bool gsrb_pair_B_ok(const float* eps, const float* rout, const float* x, const f
   return gsrb_pair_ok(g, cl) && al8(eps, rout, x, emid, r);
 }
 int gsrb_fused_B(float* eps, float* rout, float* x, const float* emid, const float* r, const float* L, const GridX& g, float w,
-                 const RedWs* ws, int slot_d, int slot_f, const ConstL& cl, hipStream_t s, const XDefer* xd) {
-  if (gsrb_pair_B_ok(eps, rout, x, emid, r, g, cl)) return gsrb_pair_B(eps, rout, x, emid, r, g, w, ws, slot_d, slot_f, cl, s, xd);
+                 const RedWs* ws, int slot_d, int slot_f, const ConstL& cl, hipStream_t s, const XDefer* xd, int out) {
+  if (gsrb_pair_B_ok(eps, rout, x, emid, r, g, cl)) return gsrb_pair_B(eps, rout, x, emid, r, g, w, ws, slot_d, slot_f, cl, s, xd, out);
+  if (out != B_BOTH) { wl_set_error("gsrb_fused_B: storing only one of r' and x needs the pair kernel"); return WL_EINVAL; }
   if (xd) { wl_set_error("gsrb_fused_B: a deferred x increment needs the pair kernel"); return WL_EINVAL; }
   if (g.nz != g.gnz) { wl_set_error("blocked smoother on a z-slab level needs the pair kernels"); return WL_EINVAL; }
   const int zc = zchunk_for(g, 3);

@@ -432,8 +432,11 @@ __global__ void __launch_bounds__(PT_N, WL_A_WAVES) k_gsrb2_A(GridX g, float* __
 
 // ------------------------------------------------------------------------------------------------------------------
 // kernel B:  colour sweep 3 ; colour sweep 4 ; increment!(ω)  [NORMS: L₁, L∞ of r' per workgroup; EPS: store the final ϵ]
+// OUT (wl::BOut): which of increment!'s two results are stored.  B_BOTH: r' and x.  B_XONLY: no store to rout is issued at all (r' lives in registers for the
+// norms; the launch leaves ϵ_mid and r untouched, so B_RONLY can produce rout later).  B_RONLY: sweeps 3 and 4 and r' as ever, rout stored; x and x_c are
+// neither loaded nor stored, no norms.  The statements that produce r' and x are the same in every mode.
 // ------------------------------------------------------------------------------------------------------------------
-template <int NORMS, int EPS>
+template <int NORMS, int EPS, int OUT = wl::B_BOTH>
 __global__ void __launch_bounds__(PT_N, WL_B_WAVES) k_gsrb2_B(GridX g, float* __restrict__ eout, float* __restrict__ rout, float* __restrict__ x, const float* __restrict__ emid,
                                                      const float* __restrict__ r, float w, int zchunk, double* __restrict__ part, float* __restrict__ pmax, wl::ConstL cl, XPro xp) {
   __shared__ float sA[2][PL_SZ];   // ϵ_mid of the newest plane
@@ -446,7 +449,7 @@ __global__ void __launch_bounds__(PT_N, WL_B_WAVES) k_gsrb2_B(GridX g, float* __
   const float c2 = cl.c[2];
   const int jpar = (t.j + g.gk) & 1;
   const int oth0 = PL_H + t.lq - 1, oth1 = t.lq + 1;
-  float2 e0 = {0.f, 0.f}, e1 = e0, e2 = e0, e3 = e0, e4 = e0, r1 = e0, r2 = e0, r3 = e0, n_e0, n_r1, n_x3, n_v3 = e0;
+  float2 e0 = {0.f, 0.f}, e1 = e0, e2 = e0, e3 = e0, e4 = e0, r1 = e0, r2 = e0, r3 = e0, n_e0, n_r1, n_x3 = e0, n_v3 = e0;
   double nsum = 0.0; float nmax = 0.f;
   const int Kbeg = t.ks - 3, Kend = t.ke + 2;
   const bool stp = t.st0 || t.st1;
@@ -455,11 +458,13 @@ __global__ void __launch_bounds__(PT_N, WL_B_WAVES) k_gsrb2_B(GridX g, float* __
     const unsigned o0 = t.oc + (unsigned)K * (unsigned)g.sz;
     n_e0 = (t.indom && K >= 0 && K <= g.nz - 1) ? ld2(emid, o0) : make_float2(0.f, 0.f);
     n_r1 = (t.indom && pint(g, K - 1)) ? ld2(r, o0 - (unsigned)g.sz) : make_float2(0.f, 0.f);
+    if (OUT != wl::B_RONLY) {
     n_x3 = (stp && (K - 3) >= t.ks && (K - 3) < t.ke) ? ld2(x, o0 - 3u * (unsigned)g.sz) : make_float2(0.f, 0.f);
     if (xp.on && stp && (K - 3) >= t.ks && (K - 3) < t.ke) n_v3 = ld2u(xp.xc, qxc + (unsigned)(dwn(g.gk + K - 3, xp.cz) - xp.cgk) * xp.csz);
+    }
   };
   fetch(Kbeg);
-  WL_SETTLE4(n_e0, n_r1, n_x3, n_v3);   // (no load pending at the loop entry: the loop top then needs no wait at all)
+  if (OUT != wl::B_RONLY) WL_SETTLE4(n_e0, n_r1, n_x3, n_v3); else WL_SETTLE2(n_e0, n_r1);   // (no load pending at the loop entry: the loop top then needs no wait at all)
   // ---- fast steps -------------------------------------------------------------------------------------------------------------
   // A step whose planes K-3..K+1 are all away from the z-walls (every z-face coefficient = c[2], iD = the "both faces open" value)
   // and inside the local array needs none of the general step's plane predicates, and — the colour a wave updates being uniform
@@ -492,7 +497,7 @@ __global__ void __launch_bounds__(PT_N, WL_B_WAVES) k_gsrb2_B(GridX g, float* __
       const unsigned pk = (unsigned)K * sz4;                        // byte offset of plane K
       n_e0 = bld2(b_em, ob0, pk + sz4);                             // (lanes outside the array read the plane's corner ghost pair)
       n_r1 = bld2(b_r, ob0, pk);
-      {
+      if (OUT != wl::B_RONLY) {
         const unsigned mo = ((K - 2) >= t.ks && (K - 2) < t.ke) ? 0u : WL_OOB_STEP;
         n_x3 = bld2(b_x, vst | mo, pk - 2u * sz4);
         if (xp.on) n_v3 = bld2(b_xc, vxc | mo, (unsigned)(dwn(g.gk + K - 2, xp.cz) - xp.cgk) * (xp.csz * 4u));
@@ -538,8 +543,8 @@ __global__ void __launch_bounds__(PT_N, WL_B_WAVES) k_gsrb2_B(GridX g, float* __
       sC[cb][t.lq] = e2.x; sC[cb][t.lq + PL_H] = e2.y;
       {   // all stores of the step, issued unconditionally (see mkbuf): counted waits instead of a drain per step
         const unsigned mo = inc ? 0u : WL_OOB_STEP;
-        bst2(b_ro, vst | mo, pk - 3u * sz4, rn);
-        bst2(b_xs, vst | mo, pk - 3u * sz4, xn);
+        if (OUT != wl::B_XONLY) bst2(b_ro, vst | mo, pk - 3u * sz4, rn);
+        if (OUT != wl::B_RONLY) bst2(b_xs, vst | mo, pk - 3u * sz4, xn);
         if (EPS && inc && stp) st2(eout, t.oc + (unsigned)(K - 3) * (unsigned)g.sz, e3, t.st0, t.st1);   // (test-only variant: its conditional store costs it the counted waits)
       }
     };
@@ -602,11 +607,11 @@ __global__ void __launch_bounds__(PT_N, WL_B_WAVES) k_gsrb2_B(GridX g, float* __
     sB[cb][t.lq] = e1.x; sB[cb][t.lq + PL_H] = e1.y;
     sC[cb][t.lq] = e2.x; sC[cb][t.lq + PL_H] = e2.y;
     // ---- all stores of the step, behind the wait for the prefetched plane (see WL_SETTLE)
-    WL_SETTLE4(n_e0, n_r1, n_x3, n_v3);
+    if (OUT != wl::B_RONLY) WL_SETTLE4(n_e0, n_r1, n_x3, n_v3); else WL_SETTLE2(n_e0, n_r1);
     if (inc) {
       const unsigned o3 = t.oc + (unsigned)(K - 3) * (unsigned)g.sz;
-      st2(rout, o3, rn, t.st0, t.st1);
-      st2(x, o3, xn, t.st0, t.st1);
+      if (OUT != wl::B_XONLY) st2(rout, o3, rn, t.st0, t.st1);
+      if (OUT != wl::B_RONLY) st2(x, o3, xn, t.st0, t.st1);
       if (EPS) st2(eout, o3, e3, t.st0, t.st1);
     }
   }
@@ -680,8 +685,9 @@ int gsrb_pair_A_pro(float* emid, float* rnew, float* x, const float* r, const fl
   WL_LAUNCH_CHECK(); return 0;
 }
 int gsrb_pair_B(float* eps, float* rout, float* x, const float* emid, const float* r, const GridX& g, float w,
-                const RedWs* ws, int slot_d, int slot_f, const wl::ConstL& cl, hipStream_t s, const wl::XDefer* xd) {
+                const RedWs* ws, int slot_d, int slot_f, const wl::ConstL& cl, hipStream_t s, const wl::XDefer* xd, int out) {
   XPro xp{};
+  if (out == wl::B_RONLY) { ws = nullptr; xd = nullptr; eps = nullptr; }   // the recompute of a skipped rout: no x, no norms, no ϵ
   if (xd) xp = XPro{xd->xc, 1, xd->w, xd->gc.nx < g.nx, xd->gc.ny < g.ny, xd->gc.gnz < g.gnz, (unsigned)xd->gc.sy, (unsigned)xd->gc.sz, xd->gc.gk, (unsigned)(xd->gc.cs * 4)};
   const int zc = zchunk2(g, 4, 3);
   const int nt = ptile_count(g.nx, g.ny, 4, 3), per = (nt + 7) >> 3, nch = (g.k1 - g.k0 + zc - 1) / zc;
@@ -689,11 +695,25 @@ int gsrb_pair_B(float* eps, float* rout, float* x, const float* emid, const floa
   const bool norms = ws && nb <= WL_MAXPART;
   double* pa = norms ? ws->pa : nullptr; float* pm = norms ? ws->pm : nullptr;
 #define WL_GB(NF, EF) hipLaunchKernelGGL((k_gsrb2_B<NF, EF>), dim3(nb), dim3(PT_N), 0, s, g, eps, rout, x, emid, r, w, zc, pa, pm, cl, xp)
+#define WL_GBO(NF, OF) hipLaunchKernelGGL((k_gsrb2_B<NF, 0, OF>), dim3(nb), dim3(PT_N), 0, s, g, eps, rout, x, emid, r, w, zc, pa, pm, cl, xp)
+  if (out == wl::B_XONLY) {
+    // (the fallback norms below read the stored array: the caller asks gsrb_pair_B_kernel_norms first)
+    if (eps || (ws && !norms)) { wl_set_error("gsrb_pair_B: the x-only form stores no ϵ and needs its norms from the kernel"); return WL_EINVAL; }
+    if (norms) WL_GBO(1, wl::B_XONLY); else WL_GBO(0, wl::B_XONLY);
+  } else if (out == wl::B_RONLY) WL_GBO(0, wl::B_RONLY);
+  else
   if (norms) { if (eps) WL_GB(1, 1); else WL_GB(1, 0); } else { if (eps) WL_GB(0, 1); else WL_GB(0, 0); }
+#undef WL_GBO
 #undef WL_GB
   if (norms) WL_TRY(wl::finalize_sum_max(*ws, (int)nb, slot_d, slot_f, s));
   else if (ws) WL_TRY(wl::norms_dev(rout, g, *ws, slot_d, slot_f, s));
   WL_LAUNCH_CHECK(); return 0;
+}
+// the launch of gsrb_pair_B for this grid takes its norms from the kernel's registers (not from the stored rout)
+bool gsrb_pair_B_kernel_norms(const GridX& g) {
+  const int zc = zchunk2(g, 4, 3);
+  const int nt = ptile_count(g.nx, g.ny, 4, 3), per = (nt + 7) >> 3, nch = (g.k1 - g.k0 + zc - 1) / zc;
+  return (unsigned)(8 * per * nch) <= WL_MAXPART;
 }
 }  // namespace WL_PNS
 

@@ -25,6 +25,23 @@ struct wl_mg {
   unsigned perdir = 0;
   bool use_constl = true;   // allow the constant-coefficient specialisations where the pattern is verified
   bool store_eps = true;    // the blocked smoother also stores the final ϵ (p.ϵ of the reference); the mom_step! composite turns it off
+  // skip_r: kernel B of the pair smoother does not store the residual where nobody reads it (wl::B_XONLY).  Acts only on a single-domain level (not dist,
+  // part, perdir) that runs the constant-coefficient pair kernels with a pending prolongation, with store_eps off and the norms coming out of the kernel.
+  //   coarse levels, inside vcycle(): always — the caller reads only coarse.x and the next restrict! overwrites coarse.r, so a coarse level's r (and what
+  //     wl_mg_level_field hands out for it) is unspecified scratch under skip_r;
+  //   finest level, inside solve(): iteration k skips iff the previous solve of the same slot (rskip_slot, set by the caller for the next solves; −1: never
+  //     skip) stopped at exactly k iterations.  If the loop goes on after a skipped store, the r-only instance (wl::B_RONLY, same arguments) produces r
+  //     before the next V-cycle; if the loop ends there, r stays stale until somebody asks for it (settle_r: wl_mg_level_field, wl_mg_smooth, wl_mg_vcycle) —
+  //     the next solve rebuilds r from scratch and forgets the debt.
+  // Off by default: wl_mg_* users see every store; the mom_step! composite turns it on (option "rskip").
+  bool skip_r = false;
+  int rskip_slot = -1;
+  int rskip_hist[2] = {0, 0};      // iterations of the last solve that stood, per slot (0: none yet — store)
+  bool r_stale = false; float r_stale_w = 0.f;      // lv[0].r was not written by the last smooth!(0): kernel B's inputs lv[0].em, lv[0].rs are intact, ω as given
+  hipStream_t r_stale_stream = nullptr;             // … and the stream that launch ran on: where a stream-less reader (wl_mg_level_field) has r produced, and waits for it
+  long n_rskip = 0, n_rskip_redo = 0;      // finest-level launches that skipped the store / r-only launches (lazy ones included)
+  int settle_r(hipStream_t s);
+  int settle_r_for_reader();
   bool use_fused = true;    // temporally blocked GaussSeidelRB! on eligible levels (wl_fused.hip)
   bool use_zsplit = true;   // body levels: constant-coefficient pair kernels on the planes away from the body, general kernels on the rest
   long zsplit_min = 16L << 20;   // ... on levels of at least this many cells (smaller ranges do not fill 256 CUs; with the 16-row pair tiles a 256³ level gains 2 %, 384³ 4 %, 512³ 7 %; 128³ levels lose)
@@ -63,7 +80,7 @@ struct wl_mg {
   bool pair_slab(const Level& v) const { return v.dist && v.g.k0 >= 3 && use_fused && !perdir && wl::gsrb_pair_ok(v.x_, v.cl); }
   ~wl_mg();
   int update(hipStream_t s);
-  int smooth(int l, int it, float w, hipStream_t s, bool want_norms = false, bool* norms_done = nullptr);
+  int smooth(int l, int it, float w, hipStream_t s, bool want_norms = false, bool* norms_done = nullptr, int bout = 0);   // bout = wl::B_XONLY: r' need not be stored (honoured where skip_r acts)
   int vcycle(int l, float w, hipStream_t s, bool defer = false);
   int flush_pending(int l, float w, hipStream_t s);
   // have_residual: r and the local Σr (ws.res_d[0]) were already produced by the caller's fused div+residual kernel

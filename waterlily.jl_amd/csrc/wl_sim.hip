@@ -597,10 +597,12 @@ struct wl_sim {
       mg->spec_tail = [&, dtl, done, s](const float* go) { return launch_tail(plan, c, dtl, go, done, s); };
       mg->spec_check_head = resjac_force_redo ? 2 : 1; n_tailspec_armed++;
     }
+    const int slot = mg->rskip_slot, hist = slot >= 0 ? mg->rskip_hist[slot] : 0;
     WL_TRY(mg->solve(2e-3, itmx, nullptr, nullptr, nullptr, s, true, nullptr, nullptr));
     h->tail_ran = mg->tail_stood; if (h->tail_ran) n_tailspec++;
     const bool due = mg->head_decided ? mg->head_due : (resjac_force_redo || wl_shift_due(mg->first_hd0, (double)wl_ninside_global(mg->lv[0].g)));
-    if (due) head_discard(h); else { head_accept(h); h->solved = true; }
+    if (due) { head_discard(h); if (slot >= 0) mg->rskip_hist[slot] = hist; }      // (a discarded solve is nobody's "rskip" history)
+    else { head_accept(h); h->solved = true; }
     return 0;
   }
   int head_read_back(Head* h, hipStream_t s) {
@@ -653,6 +655,9 @@ struct wl_sim {
   }
   int project(const ProjCall& c, hipStream_t s) {
     const float dtl = c.w * dt.back();
+    // "rskip": the solves of this projection keep their own history of where they stopped — the predictor's (Δt weight 1) and the corrector's (½) differ
+    struct RSlot { wl_mg* m; ~RSlot() { m->rskip_slot = -1; } } rslot{mg};
+    mg->rskip_slot = c.w == 1.f ? 0 : 1;
     df.cfl_done = false;
     if (df.p_scale_pending != 0.f && !head_fused_ok()) WL_TRY(materialise_p(s));          // (the fused head was switched off since the tail ran: back-off, an option)
     WL_TRY(sync_u(s));                                                                     // div(u) reads the halo planes
@@ -833,6 +838,7 @@ static int sim_create_common(wl_sim** out, const wl_sim_desc* desc, wl_comm* com
     if (rc != 0) { delete s; *out = nullptr; return rc; }
   }
   s->mg->store_eps = false;   // p.ϵ is pure scratch on the time-step path
+  s->mg->skip_r = true;       // … and so is the residual a solve ends on, and every coarse level's (option "rskip")
   if (slab && s->G.k0 >= 2 && s->G.nz - s->G.k1 >= 2) s->mg->x_halo_depth = 2;   // z-slab: the fused projection head recomputes the residual of the neighbour's boundary plane (x two planes deep)
   *out = s; return 0;
 }
@@ -864,6 +870,7 @@ static double placement_score(wl_sim* s) {
   // initial condition / init_flow will write again)
   s->mg->n.resize(n0); s->n_resjac = 0; s->n_resjac_redo = 0; s->resjac_redo_run = 0; s->resjac_backoff = false; s->df.cfl_done = false;
   s->mg->log_r1.clear(); s->mg->log_rinf.clear(); s->mg->log_w.clear();
+  s->mg->rskip_hist[0] = s->mg->rskip_hist[1] = 0; s->mg->n_rskip = s->mg->n_rskip_redo = 0;
   return rc == 0 ? (double)ms : 1e30;
 }
 static double g_last_placement[8]; static int g_last_placement_n = 0;
@@ -955,6 +962,7 @@ int wl_sim_set_option(wl_sim* s, const char* name, int value) {
   if (n == "headspec") { s->use_headspec = value != 0; return 0; }                             // the first V-cycle is queued behind the fused head before Σr is known (default 1)
   if (n == "bcdefer") { s->use_bcdefer = value != 0; return 0; }                               // mom_step!: BC! after the fused conv_diff!+BDIM! left to the projection (its head reads U on the wall-normal faces, its tail rewrites the boundary); default 1
   if (n == "pdefer") { s->use_pdefer = value != 0; return 0; }                                 // mom_step!: a projection tail whose p = x/Δt is read next by a fused head of the same call does not store it (default 1)
+  if (n == "rskip") { WL_TRY(s->mg->settle_r_for_reader()); s->mg->skip_r = value != 0; return 0; }      // smoother kernel B does not store the residual nobody reads: every coarse level's, and the finest level's in the iteration the slot's last solve stopped at (default 1); 0: every store
   if (n == "tailwide") { s->use_tailwide = value != 0; return 0; }                             // the projection tails with four cells per thread and 16-byte accesses where the shape allows (default 1); 0: the one- and two-cell kernels
   if (n == "tailfuse") { s->use_tailfuse = value != 0; if (value != 0) s->tailfuse_min = 0; return 0; }   // mom_step!: the first projection's u −= L∇x + BC! inside the corrector's conv_diff! (default 1 on grids of at least "tailfuse_min" cells; an explicit 1 also drops that gate)
   if (n == "tailfuse_min") { if (value < 0) { wl_set_error("tailfuse_min: interior cells, >= 0"); return WL_EINVAL; } s->tailfuse_min = value; return 0; }   // interior-cells gate of "tailfuse" (default 16 Mi = 256³; tests: 0 or a small whole-tile shape)
@@ -986,6 +994,8 @@ int wl_sim_counter(wl_sim* s, const char* name, long* out) {
   if (n == "bcdefer") { *out = s->n_bcdefer; return 0; }
   if (n == "pdefer") { *out = s->n_pdefer; return 0; }
   if (n == "tailwide") { *out = s->n_tailwide; return 0; }
+  if (n == "rskip") { *out = s->mg->n_rskip; return 0; }
+  if (n == "rskip_redo") { *out = s->mg->n_rskip_redo; return 0; }
   if (n == "tailspec") { *out = s->n_tailspec; return 0; }
   if (n == "tailspec_armed") { *out = s->n_tailspec_armed; return 0; }
   if (n == "xdefer") { *out = s->mg->last_xdefer; return 0; }
