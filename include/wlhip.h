@@ -330,6 +330,39 @@ int wl_sim_viscous_force_sphere(wl_sim* s, const float* center, float R, double*
 int wl_sim_flow_stats(wl_sim* s, const float* host_U, double out[3], void* stream);
 int wl_sim_flow_fields(wl_sim* s, const float* host_U, float* ke, float* omega3, float* omega_mag, float* lambda2, void* stream);
 
+/* ---- point samples, per-step probe records, tracer particles: src/util.jl:17-43 -------------------------------------------------
+ * interp.(x, Ref(arr)) :20-43 on the device.  x: n×D point-major (a Julia Vector{SVector{D,Float32}}); out: n×ncomp point-major.
+ * ncomp = 1: arr is a scalar array (Ng...), `interp(x, arr)` :26-28.  ncomp = D: arr is the staggered vector array (Ng...,D), `interp(x, varr)` :20-25 —
+ * component i is queried at x + ½·eᵢ (shift :23).  Queries are clamped to [0, Ng_d − 2] per direction (_interp_clamp :17-18), so every x is legal (a NaN
+ * coordinate is taken as 0); then x += 1.5, i = floor(x), y = x − i and the weighted sum over the 2^D corners in CartesianIndices order (_interp :29-43; the
+ * written order — @fastmath @simd leaves the reference's own open).  One thread per point, one launch; n = 0 returns 0 without one.  out may not overlap arr
+ * or x (WL_EINVAL); ncomp other than 1 or D and a z-slab wl_grid return WL_EINVAL — as for every entry point of this section.
+ * The last argument of wl_interp, wl_sim_sample and wl_advect is the stream (a hipStream_t as void*, NULL = default), with the contract of the Conventions:
+ * the call is asynchronous on it.  Their stream-contract scenarios are tests/test_gpu_streams_interp.py. */
+int wl_interp(float* out, const float* arr, const wl_grid* g, const float* x, size_t n, int ncomp, void* hip_stream);
+/* the same at n device points of a handle's CURRENT u and p (the arrays wl_sim_field(s,"u") and "p" name: roles rotate): u_out n×D or NULL, p_out n or NULL,
+ * one launch for both */
+int wl_sim_sample(wl_sim* s, const float* x, size_t n, float* u_out, float* p_out, void* hip_stream);
+/* m probe points (host, m×D) and room for `capacity` steps.  After every completed mom_step! of this handle (wl_sim_mom_step, each step of wl_sim_mom_steps) one
+ * record is appended on the device: m×(D+1) floats, per probe u(x) (D values) then p(x), interpolated as wl_sim_sample does from that step's final u and p.
+ * One launch per step on the step's stream, behind the second projection and ahead of CFL; no host round trip; with probes set the corrector's projection tail
+ * stores p where option "pdefer" would skip it (same bits on every cell).  A full buffer drops new records (wl_sim_counter "probe_dropped"; "probe_records":
+ * those held).  m = 0 switches recording off.  Setting probes discards records not read yet.  Waits for the device. */
+int wl_sim_set_probes(wl_sim* s, const float* host_x, int m, int capacity);
+/* copies the records taken since the last read (oldest first) to the host, returns their number in *n_records and the index into flow.Δt of the first one's
+ * step in *first_step (record r belongs to step first_step + r; its end time is sum(Δt[1:first_step+r+1])); empties the buffer.  Synchronises the stream the
+ * records were taken on.  host_out NULL: a query — the two numbers only, nothing is emptied.  cap_records below the number held: WL_EINVAL, nothing read. */
+int wl_sim_read_probes(wl_sim* s, float* host_out, int cap_records, int* n_records, int* first_step);
+/* one step of a particle swarm (n×D device positions): x⁰ ← x;  x* = x⁰ + Δt·u⁰(x⁰);  x ← x⁰ + ½Δt·(u⁰(x⁰) + u¹(x*)), u(·) the interp of a vector array above.
+ * For a direction j in perdir_mask, x_j is wrapped into [0, N_j) afterwards (N_j interior cells); other coordinates are left free — interp clamps the query,
+ * not the particle.  x, x_prev and the velocity arrays may not overlap (WL_EINVAL). */
+int wl_advect(float* x, float* x_prev, const float* u0, const float* u1, const wl_grid* g, size_t n, float dt, unsigned perdir_mask, void* hip_stream);
+/* tracers of a handle: after every completed mom_step! it calls wl_advect with u0 = the array in the u⁰ role (the velocity the step started from,
+ * src/Flow.jl:157), u1 = the step's final u and the Δt the step ran with (the reference's pathline extension advances with Δt[end-1] after the step) — one
+ * launch per step, independent of the probes'.  The handle owns x and x⁰ (n×D each, x⁰ = x until the first step); n = 0 frees them.  Waits for the device. */
+int wl_sim_set_tracers(wl_sim* s, const float* host_x, size_t n);
+float* wl_sim_tracers(wl_sim* s, int which /*0 position, 1 position⁰*/, size_t* n);   /* device pointers, for drawing or wl_d2h */
+
 /* ---- composite bodies: closed-form leaves under rigid maps, combined by set operations (src/Body.jl:91-107, RigidMap.jl) -------
  * A wl_bodyset is a postfix program of at most WL_BODYSET_MAX nodes (evaluation stack at most WL_BODYSET_STACK deep, final depth 1).
  * Leaf kinds are those of wl_body plus WL_BODY_CAPSULE: sdf = |ξ−p|−R, p the point of the segment c ± h·m (m the body-frame axis,

@@ -10,6 +10,7 @@ from .poisson import (pcg_, poisson_solver_, GaussSeidelRB_, Jacobi_, L1, Linf, 
                       residual_, restrict_, restrictL_, set_diag_, smooth_, update_)
 from .metrics import (MeanFlow, curl_, flow_fields_, flow_stats, helicity_, ke_, lambda2_, load_checkpoint, omega_, omega_mag_, omega_theta_,  # noqa: F401
                       save_checkpoint)
+from .interp import advect_, interp, interp_  # noqa: F401
 from .simulation import (FusedSimulation, Simulation, measure_, pressure_force, pressure_moment, viscous_force,  # noqa: F401
                          viscous_moment)
 from . import bodies  # noqa: F401,E402

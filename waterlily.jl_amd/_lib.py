@@ -206,6 +206,13 @@ SIGNATURES = {
     "wl_sim_pressure_force_bodyset": (i32, [P, C.POINTER(f32), C.POINTER(wl_bodyset), C.POINTER(f64), P]),
     "wl_sim_viscous_force_bodyset": (i32, [P, C.POINTER(f32), C.POINTER(wl_bodyset), C.POINTER(f64), P]),
     "wl_sim_viscous_force_sphere": (i32, [P, C.POINTER(f32), f32, C.POINTER(f64), P]),
+    "wl_interp": (i32, [P, P, G, P, sz, i32, P]),
+    "wl_sim_sample": (i32, [P, P, sz, P, P, P]),
+    "wl_sim_set_probes": (i32, [P, C.POINTER(f32), i32, i32]),
+    "wl_sim_read_probes": (i32, [P, C.POINTER(f32), i32, C.POINTER(i32), C.POINTER(i32)]),
+    "wl_advect": (i32, [P, P, P, P, G, sz, f32, u32, P]),
+    "wl_sim_set_tracers": (i32, [P, C.POINTER(f32), sz]),
+    "wl_sim_tracers": (P, [P, i32, C.POINTER(sz)]),
 }
 
 _lib = None

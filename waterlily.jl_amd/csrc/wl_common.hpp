@@ -268,6 +268,10 @@ int metrics_omega_theta(float* out, const float* u, const GridX& g, const float*
 int metrics_curl(float* out, const float* u, const GridX& g, int i, hipStream_t s);                                                   // i = 1..3 (2-D: 3)
 int metrics_helicity(float* out, const float* u, const float* w3, const GridX& g, hipStream_t s);
 int metrics_stats_dev(const float* u, const GridX& g, const float* U, const RedWs& ws, hipStream_t s);   // Σke, Σ½|ω|² -> ws.res_d[0..1], max|ω| -> ws.res_f[0]; two launches
+// interp(x,arr) of src/util.jl:17-43 at n device points (wl_interp.hip): vec (Ng...,D) -> out_v[t·ldv + i], sca (Ng...) -> out_s[t·lds], either may be null; one launch.
+// Single-domain grids only, else WL_EINVAL before any launch.  advect: one predictor-corrector step of a particle swarm through u0 and u1 (wlhip.h wl_advect).
+int interp_points(const float* vec, const float* sca, const GridX& g, const float* x, size_t n, float* out_v, long ldv, float* out_s, long lds, hipStream_t s);
+int advect(float* x, float* x_prev, const float* u0, const float* u1, const GridX& g, size_t n, float dt, unsigned per, hipStream_t s);
 int bc_vec_fn(float* a, const float* Ub, const GridX& g, int saveexit, unsigned per, hipStream_t s);
 int add_field(float* r, const float* gfield, size_t n, hipStream_t s);
 int meanflow_update(float* P, float* U, float* UU, const float* p, const float* u, const GridX& g, float e, hipStream_t s);

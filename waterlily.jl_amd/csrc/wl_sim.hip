@@ -288,7 +288,7 @@ struct wl_sim {
   // makes memory current for a reader outside the step (fields handed out, force read-outs, wl_sim_phase, a failed step).  Between calls nothing is pending but, on
   // slabs, the exchange — "a call never returns with the divisor pending", every projection ends with BC! applied — so this launches nothing there.
   int settle(hipStream_t s) { WL_TRY(sync_u(s)); WL_TRY(materialise_p(s)); return flush_bc(s); }
-  ~wl_sim() { if (df.u_pending && comm && comm->cs) (void)hipStreamSynchronize(comm->cs); if (own_mg) delete mg; if (own) (void)hipFree(own); if (exit_sc) (void)hipFree(exit_sc); if (farmask) (void)hipFree(farmask); if (mnear) (void)hipFree(mnear); if (mneedf) (void)hipFree(mneedf); if (mm0var) (void)hipFree(mm0var); }
+  ~wl_sim() { if (df.u_pending && comm && comm->cs) (void)hipStreamSynchronize(comm->cs); if (own_mg) delete mg; if (own) (void)hipFree(own); if (exit_sc) (void)hipFree(exit_sc); if (farmask) (void)hipFree(farmask); if (mnear) (void)hipFree(mnear); if (mneedf) (void)hipFree(mneedf); if (mm0var) (void)hipFree(mm0var); free_probes(); free_tracers(); }
 
   // BC!(u) on the physical faces this rank holds, then the z-halo planes (depth 2: QUICK reads f[I-2δ], src/Flow.jl:8)
   // On slabs the exchange runs on the communicator's own stream; the compute stream waits for it (sync_u) only where the halo
@@ -542,7 +542,7 @@ struct wl_sim {
   }
   bool skip_p_now(const ProjCall& c) const {      // decided per launch: a back-off during the head withdraws it
     if (!pdefer_ok()) return false;
-    if (c.with_cfl) return c.step_follows;                          // the corrector's tail: the next reader is the next step's head
+    if (c.with_cfl) return c.step_follows && !probe_m;              // the corrector's tail: the next reader is the next step's head — unless the probe record of this step reads p first
     return c.corrector_follows && (!p_home || c.step_follows || p == p_home);   // the predictor's tail: the corrector's head (caller-owned p, last step of the call: see the parity rule above)
   }
   // go != nullptr: queued inside the solver loop ahead of its read — runs iff the flag says "converged"; a gated tail that was withheld is launched again with go = nullptr.
@@ -693,8 +693,35 @@ struct wl_sim {
     dt.push_back(std::fmin(10.f, 1.0f / (mx + 5 * d.nu)));
     return 0;
   }
+  // ---- observers of a completed step (wl_sim_set_probes, wl_sim_set_tracers; kernels in wl_interp.hip).  Both read the step's final u — and the probes p, the tracers
+  // the array in the u⁰ role, which no kernel of the step writes: it still holds the velocity the step started from (src/Flow.jl:157) — after the second projection
+  // and before CFL; neither writes anything the step reads, so a handle with observers computes the bits of one without.  One launch each per step, none when unset.
+  float *probe_x = nullptr, *probe_rec = nullptr;      // device: m×D points; capacity records of m×(D+1) floats
+  int probe_m = 0, probe_cap = 0, probe_n = 0;         // probes, records the buffer takes, records held
+  long probe_first = 0, n_probe_dropped = 0;           // index into Δt of the first held record's step; records a full buffer refused
+  float *tr_x = nullptr, *tr_x0 = nullptr; size_t tr_n = 0;      // tracer positions and positions before the last step (n×D each)
+  hipStream_t obs_stream = nullptr;                    // the stream the last record went to (wl_sim_read_probes waits for it)
+  long n_step_launches = 0;                            // kernel launches of this handle's mom_step! calls (wl_sim_counter "launches")
+  void free_probes() { if (probe_x) (void)hipFree(probe_x); if (probe_rec) (void)hipFree(probe_rec); probe_x = probe_rec = nullptr; probe_m = probe_cap = probe_n = 0; }
+  void free_tracers() { if (tr_x) (void)hipFree(tr_x); if (tr_x0) (void)hipFree(tr_x0); tr_x = tr_x0 = nullptr; tr_n = 0; }
+  int observe(hipStream_t s) {      // dt.back() is still the Δt this step ran with: cfl appends the next one afterwards
+    if (probe_m) {
+      WL_TRY(materialise_p(s));     // (guard: skip_p_now keeps the corrector's tail storing while probes are set)
+      if (probe_n == probe_cap) n_probe_dropped++;
+      else {
+        float* rec = probe_rec + (size_t)probe_n * probe_m * (d.D + 1);
+        WL_TRY(wl::interp_points(u, p, G, probe_x, (size_t)probe_m, rec, d.D + 1, rec + d.D, d.D + 1, s));
+        if (probe_n++ == 0) probe_first = (long)dt.size() - 1;
+        obs_stream = s;
+      }
+    }
+    if (tr_n) WL_TRY(wl::advect(tr_x, tr_x0, u0, u, G, tr_n, dt.back(), d.perdir_mask, s));
+    return 0;
+  }
   int mom_step(hipStream_t s, bool more_follow = false) {
+    const long l0 = g_wl_launches;
     const int rc = mom_step_body(s, more_follow);
+    n_step_launches += g_wl_launches - l0;
     // A failed step leaves nothing pending for the next call to take.  BC! of a u nobody can use is dropped, not launched.
     // The divisor is applied: pdefer is single-domain, so settle's slab wait, the only step before it, does nothing there.
     // On slabs that wait (no launch) lets the exchange finish before its flag goes; the rest of the record is cleared.
@@ -723,6 +750,7 @@ struct wl_sim {
     WL_TRY(project(ProjCall::step_first(more_follow), s));
     WL_TRY(correct(s));
     WL_TRY(project(ProjCall::step_second(more_follow), s));
+    WL_TRY(observe(s));      // u and p are final; ahead of the CFL reduction
     return cfl(s, more_follow);
   }
 };
@@ -1016,6 +1044,9 @@ int wl_sim_counter(wl_sim* s, const char* name, long* out) {
   if (n == "part") { *out = s->mg->lv[0].part ? 1 : 0; return 0; }                 // the finest level's z-split: decided / planes [za, zb] off the constant pattern
   if (n == "part_za") { *out = s->mg->lv[0].za; return 0; }
   if (n == "part_zb") { *out = s->mg->lv[0].zb; return 0; }
+  if (n == "launches") { *out = s->n_step_launches; return 0; }                    // kernel launches of this handle's mom_step! calls so far
+  if (n == "probe_records") { *out = s->probe_n; return 0; }                       // probe records held / refused by a full buffer
+  if (n == "probe_dropped") { *out = s->n_probe_dropped; return 0; }
   wl_set_error("unknown counter " + n); return WL_EINVAL;
 }
 int wl_sim_set_forcing(wl_sim* s, const float* U1, const float* a0, const float* a1) {
@@ -1209,6 +1240,66 @@ int wl_sim_flow_fields(wl_sim* s, const float* U, float* ke, float* w3, float* w
   if (s->comm) { wl_set_error("wl_sim_flow_fields: z-slab handles are not supported (single domain only)"); return WL_EINVAL; }
   WL_TRY(s->settle(wl_stream(st)));
   return wl::metrics_fields(s->u, s->G, U, ke, w3, wmag, l2, wl_stream(st));
+}
+// interp at n points of the handle's CURRENT u and p (roles rotate), both outputs in one launch (wl_interp.hip)
+int wl_sim_sample(wl_sim* s, const float* x, size_t n, float* u_out, float* p_out, void* st) {
+  WL_CHECK(s, "wl_sim_sample: null handle");
+  if (s->comm) { wl_set_error("wl_sim_sample: z-slab handles are not supported (single domain only)"); return WL_EINVAL; }
+  WL_CHECK(u_out || p_out, "wl_sim_sample: both outputs are null");
+  if (n == 0) return 0;
+  WL_CHECK(x, "wl_sim_sample: null points");
+  WL_TRY(s->settle(wl_stream(st)));
+  const size_t D = (size_t)s->d.D, nc = (size_t)s->G.cs;
+  auto ov = [](const float* a, size_t na, const float* b, size_t nb) { return a && b && a < b + nb && b < a + na; };
+  WL_CHECK(!ov(u_out, n * D, s->u, nc * D) && !ov(u_out, n * D, s->p, nc) && !ov(p_out, n, s->u, nc * D) && !ov(p_out, n, s->p, nc) && !ov(u_out, n * D, x, n * D) &&
+           !ov(p_out, n, x, n * D) && !ov(u_out, n * D, p_out, n), "wl_sim_sample: an output overlaps the flow arrays, the points or the other output");
+  return wl::interp_points(u_out ? s->u : nullptr, p_out ? s->p : nullptr, s->G, x, n, u_out, (long)D, p_out, 1, wl_stream(st));
+}
+int wl_sim_set_probes(wl_sim* s, const float* host_x, int m, int capacity) {
+  WL_CHECK(s && m >= 0, "wl_sim_set_probes: null handle or negative m");
+  if (s->comm) { wl_set_error("wl_sim_set_probes: z-slab handles are not supported (single domain only)"); return WL_EINVAL; }
+  WL_CHECK(m == 0 || (host_x && capacity >= 1), "wl_sim_set_probes: null points or capacity < 1");
+  WL_HIP(hipDeviceSynchronize());      // records may still be in flight on the stream of the last step
+  s->free_probes(); s->n_probe_dropped = 0;
+  if (m == 0) return 0;
+  const size_t nx = (size_t)m * s->d.D, nr = (size_t)capacity * m * (s->d.D + 1);
+  WL_HIP(hipMalloc((void**)&s->probe_x, nx * sizeof(float)));
+  if (hipMalloc((void**)&s->probe_rec, nr * sizeof(float)) != hipSuccess) { s->free_probes(); wl_set_error("wl_sim_set_probes: hipMalloc failed for the record buffer"); return (int)hipErrorOutOfMemory; }
+  WL_HIP(hipMemcpy(s->probe_x, host_x, nx * sizeof(float), hipMemcpyHostToDevice));
+  s->probe_m = m; s->probe_cap = capacity;
+  return 0;
+}
+int wl_sim_read_probes(wl_sim* s, float* host_out, int cap_records, int* n_records, int* first_step) {
+  WL_CHECK(s && n_records && first_step, "wl_sim_read_probes: null handle or result");
+  *n_records = s->probe_n; *first_step = (int)s->probe_first;
+  if (!host_out) return 0;             // a query: nothing is copied, the buffer keeps its records
+  WL_CHECK(cap_records >= s->probe_n, "wl_sim_read_probes: host_out takes fewer records than the buffer holds (nothing was read)");
+  if (s->probe_n) {
+    WL_HIP(hipMemcpyAsync(host_out, s->probe_rec, (size_t)s->probe_n * s->probe_m * (s->d.D + 1) * sizeof(float), hipMemcpyDeviceToHost, s->obs_stream));
+    WL_HIP(hipStreamSynchronize(s->obs_stream));
+  }
+  s->probe_n = 0;
+  return 0;
+}
+int wl_sim_set_tracers(wl_sim* s, const float* host_x, size_t n) {
+  WL_CHECK(s, "wl_sim_set_tracers: null handle");
+  if (s->comm) { wl_set_error("wl_sim_set_tracers: z-slab handles are not supported (single domain only)"); return WL_EINVAL; }
+  WL_CHECK(n == 0 || host_x, "wl_sim_set_tracers: null points");
+  WL_HIP(hipDeviceSynchronize());      // the last step's launch may still be moving the old swarm
+  s->free_tracers();
+  if (n == 0) return 0;
+  const size_t nb = n * (size_t)s->d.D * sizeof(float);
+  WL_HIP(hipMalloc((void**)&s->tr_x, nb));
+  if (hipMalloc((void**)&s->tr_x0, nb) != hipSuccess) { s->free_tracers(); wl_set_error("wl_sim_set_tracers: hipMalloc failed"); return (int)hipErrorOutOfMemory; }
+  WL_HIP(hipMemcpy(s->tr_x, host_x, nb, hipMemcpyHostToDevice));
+  WL_HIP(hipMemcpy(s->tr_x0, host_x, nb, hipMemcpyHostToDevice));      // position⁰ = position until the first step
+  s->tr_n = n;
+  return 0;
+}
+float* wl_sim_tracers(wl_sim* s, int which, size_t* n) {
+  if (!s || (which != 0 && which != 1)) return nullptr;
+  if (n) *n = s->tr_n;
+  return which == 0 ? s->tr_x : s->tr_x0;
 }
 int wl_sim_viscous_force_sphere(wl_sim* s, const float* c, float R, double* out, void* st) { const wl_body b = sphere_body(c, R); return wl_sim_viscous_force_body(s, &b, out, st); }
 }  // extern "C"

@@ -401,6 +401,63 @@ function flow_stats(u::HA; U=nothing)
     (out[1], out[2], out[3])
 end
 
+# point samples (src/util.jl:17-43).  The reference's GPU form is the broadcast `WaterLily.interp.(x, Ref(arr))` over a device vector of
+# SVector{D,Float32} (docstring :8-15).  A HipArray holds Float32 only, so the device vector of points is a HipPoints{D}: a D×n HipArray read as n
+# SVectors — byte-identical to a Vector{SVector{D,Float32}} (HipPoints(xs) uploads one).  The broadcast is intercepted at `broadcasted`, before any
+# broadcast style is consulted (no BroadcastStyle method is added: the rules of the desk check above stay as they are), and goes to wl_interp: a scalar
+# array returns a HipArray of n values, the staggered vector array a HipPoints{D} of n interpolated vectors.
+# (Desk-checked only, like the rest of this file: no Julia runtime was available where the library is built and tested.)
+struct HipPoints{D} <: AbstractVector{WaterLily.SVector{D,Float32}}
+    data::HipArray{Float32,2}                                       # D×n, point-major in memory
+end
+HipPoints(xs::AbstractVector{WaterLily.SVector{D,Float32}}) where {D} = HipPoints{D}(HipArray(collect(reshape(reinterpret(Float32, collect(xs)), D, length(xs)))))
+Base.size(x::HipPoints) = (size(x.data, 2),)
+Base.getindex(x::HipPoints{D}, i::Int) where {D} = WaterLily.SVector{D,Float32}(ntuple(d -> x.data[d + (i - 1) * D], D))      # scalar transfers: tests only
+Base.Array(x::HipPoints{D}) where {D} = collect(reinterpret(WaterLily.SVector{D,Float32}, vec(Array(x.data))))
+function interp_points(x::HipPoints{D}, arr::HA) where {D}
+    n = length(x); vec = ndims(arr) == D + 1
+    @assert ndims(arr) == D || (vec && size(arr, D + 1) == D) "interp: arr must be a scalar array (Ng...) or the vector array (Ng...,D) of the points' dimension"
+    out = vec ? HipArray{Float32,2}(undef, (D, n)) : HipArray{Float32,1}(undef, (n,))
+    chk(ccall((:wl_interp, libwlhip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Ref{WlGrid}, Ptr{Cfloat}, Csize_t, Cint, Ptr{Cvoid}),
+              out.ptr, arr.ptr, vec ? vgrid(arr) : sgrid(arr), x.data.ptr, n, Cint(vec ? D : 1), C_NULL))
+    vec ? HipPoints{D}(out) : out
+end
+Base.Broadcast.broadcasted(::typeof(WaterLily.interp), x::HipPoints, arr::Base.RefValue{<:HA}) = interp_points(x, arr[])
+# (u, p) at the points from the composite's CURRENT u and p, one launch
+function sample(b::HipMultiLevel, x::HipPoints{D}) where {D}
+    @assert b.sim != C_NULL "sample: take a step first (the composite handle is created by the first mom_step!)"
+    n = length(x); u = HipArray{Float32,2}(undef, (D, n)); p = HipArray{Float32,1}(undef, (n,))
+    chk(ccall((:wl_sim_sample, libwlhip), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Csize_t, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cvoid}), b.sim, x.data.ptr, n, u.ptr, p.ptr, C_NULL))
+    HipPoints{D}(u), p
+end
+# probe records inside mom_step!: m points, room for `capacity` steps; read_probes returns (first step's index into flow.Δt (1-based), records (D+1)×m×k)
+function set_probes!(b::HipMultiLevel, xs::AbstractVector{WaterLily.SVector{D,Float32}}, capacity::Integer) where {D}
+    @assert b.sim != C_NULL "set_probes!: take a step first (the composite handle is created by the first mom_step!)"
+    h = collect(reshape(reinterpret(Float32, collect(xs)), D * length(xs)))
+    chk(ccall((:wl_sim_set_probes, libwlhip), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Cint, Cint), b.sim, h, Cint(length(xs)), Cint(capacity)))
+end
+function read_probes(b::HipMultiLevel, D::Integer, m::Integer)
+    k = Ref{Cint}(0); first = Ref{Cint}(0)
+    chk(ccall((:wl_sim_read_probes, libwlhip), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Cint, Ref{Cint}, Ref{Cint}), b.sim, Ptr{Cfloat}(C_NULL), Cint(0), k, first))
+    rec = Array{Float32,3}(undef, D + 1, m, Int(k[]))
+    chk(ccall((:wl_sim_read_probes, libwlhip), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Cint, Ref{Cint}, Ref{Cint}), b.sim, rec, k[], k, first))
+    Int(first[]) + 1, rec
+end
+# tracer particles the composite advances after every step (the reference's pathline extension: position, position⁰, Δt[end-1])
+function set_tracers!(b::HipMultiLevel, xs::AbstractVector{WaterLily.SVector{D,Float32}}) where {D}
+    @assert b.sim != C_NULL "set_tracers!: take a step first (the composite handle is created by the first mom_step!)"
+    h = collect(reshape(reinterpret(Float32, collect(xs)), D * length(xs)))
+    chk(ccall((:wl_sim_set_tracers, libwlhip), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Csize_t), b.sim, h, length(xs)))
+end
+function tracers(b::HipMultiLevel, D::Integer, which::Integer=0)      # non-owning view of position (0) / position⁰ (1)
+    n = Ref{Csize_t}(0)
+    p = ccall((:wl_sim_tracers, libwlhip), Ptr{Cfloat}, (Ptr{Cvoid}, Cint, Ref{Csize_t}), b.sim, Cint(which), n)
+    HipPoints{D}(HipArray{Float32,2}(p, (Int(D), Int(n[]))))
+end
+advect!(x::HipPoints{D}, x⁰::HipPoints{D}, u⁰::HA, u::HA, Δt; perdir=()) where {D} =
+    (chk(ccall((:wl_advect, libwlhip), Cint, (Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ref{WlGrid}, Csize_t, Cfloat, Cuint, Ptr{Cvoid}),
+               x.data.ptr, x⁰.data.ptr, u⁰.ptr, u.ptr, vgrid(u), length(x), Cfloat(Δt), pmask(perdir), C_NULL)); x)
+
 # ---- bodies ---------------------------------------------------------------------------------------------------------------------------
 measure!(::HFlow, ::NoBody; kwargs...) = nothing                 # src/Body.jl:83 (resolves the ambiguity with the generic method below)
 # Any AbstractBody whose `measure` is a Julia closure (AutoBody, SetBody, …): the reference's own measure! (src/Body.jl:28-51) runs on

@@ -178,6 +178,12 @@ class Simulation:
         """`@inside out[I] = <name>(I,flow.u)` — see FusedSimulation.metric; out="sigma" writes into flow.σ"""
         return _metric_leaf(self.flow.u, self.flow.sigma, name, out, **kw)
 
+    def sample(self, points):
+        """(interp.(x, Ref(flow.u)), interp.(x, Ref(flow.p))) at the (n, D) points x   src/util.jl:20-43"""
+        from .interp import interp, points as _points
+        x = _points(points, self.flow.D)
+        return interp(self.flow.u, x), interp(self.flow.p, x)
+
     def pressure_force(self):
         return pressure_force(self.flow, self.body)
 
@@ -336,7 +342,7 @@ class FusedSimulation:
         check(lib().wl_sim_set_option(self._h, name.encode(), int(value)))
 
     def counter(self, name):
-        """path counters of the handle (include/wlhip_bench.h wl_sim_counter): "resjac", "resjac_redo", "resjac_backoff", "xdefer", "tailfuse", "bcdefer", "pdefer", "tailwide", "rskip", "rskip_redo", "tailspec", "tailspec_armed"; "tailfuse_min" reads the size gate of "tailfuse" in force;
+        """path counters of the handle (include/wlhip_bench.h wl_sim_counter): "resjac", "resjac_redo", "resjac_backoff", "xdefer", "tailfuse", "bcdefer", "pdefer", "tailwide", "rskip", "rskip_redo", "tailspec", "tailspec_armed", "launches", "probe_records", "probe_dropped"; "tailfuse_min" reads the size gate of "tailfuse" in force;
         with a body: "hybrid", "body_tile", "mask_valid", "part", "part_za", "part_zb" and the mask census "mask_near", "mask_needf_only", "mask_m0var_only",
         "mask_clean_in_box", "dirty_z0", "dirty_z1", "near_b0", "near_b1", "near_k0", "near_k1" """
         v = C.c_long(0)
@@ -510,6 +516,60 @@ class FusedSimulation:
         else:
             check(L.wl_omega_theta(ptr(out), u, C.byref(g), _x0(kw["z"], 3), _x0(kw["center"], 3), stream()))
         return out
+
+    def sample(self, points):
+        """(u, p) = (interp.(x, Ref(flow.u)), interp.(x, Ref(flow.p))) at the (n, D) points x, as device arrays (n, D) and (n,): one launch on the
+        handle's current u and p (src/util.jl:20-43) — a wake probe or a line cut without a field leaving the device"""
+        import torch
+        from .interp import _pp, points as _points
+        x = _points(points, self.D)
+        n = x.shape[0]
+        u = torch.empty((n, self.D), dtype=torch.float32, device=x.device)
+        p = torch.empty((n,), dtype=torch.float32, device=x.device)
+        check(lib().wl_sim_sample(self._h, _pp(x), n, _pp(u), _pp(p), stream()))
+        return u, p
+
+    def set_probes(self, points, capacity):
+        """record u and p at the (m, D) host points after every completed step of this handle — mom_step_ and each step inside mom_steps_ — for up to
+        `capacity` steps between two read_probes(); points=None (or empty) switches recording off"""
+        x = np.zeros((0, self.D), dtype=np.float32) if points is None else np.ascontiguousarray(np.asarray(points, dtype=np.float32)).reshape(-1, self.D)
+        self._probe_m = int(x.shape[0])
+        check(lib().wl_sim_set_probes(self._h, x.ctypes.data_as(C.POINTER(C.c_float)), self._probe_m, int(capacity)))
+
+    def read_probes(self):
+        """(t, u[k,m,D], p[k,m]) of the k records taken since the last read, oldest first; t[r] is time(flow) at the end of record r's step (the
+        Float32 running sum of the Δt history, as time() forms it).  Empties the buffer."""
+        m, D = getattr(self, "_probe_m", 0), self.D
+        k, first = C.c_int(0), C.c_int(0)
+        check(lib().wl_sim_read_probes(self._h, None, 0, C.byref(k), C.byref(first)))
+        rec = np.empty((k.value, m, D + 1), dtype=np.float32)
+        check(lib().wl_sim_read_probes(self._h, rec.ctypes.data_as(C.POINTER(C.c_float)), k.value, C.byref(k), C.byref(first)))
+        ends = np.cumsum(np.asarray(self.dt, dtype=np.float32), dtype=np.float32)      # ends[j] = sum(Δt[1:j+1]), summed in order in Float32
+        t = ends[first.value:first.value + k.value].astype(np.float64)
+        return t, rec[:, :, :D].copy(), rec[:, :, D].copy()
+
+    def set_tracers(self, points):
+        """a swarm of tracer particles at the (n, D) host points, advanced by every completed step of this handle (wl_advect with u⁰, the final u and
+        the step's Δt); points=None (or empty) removes it"""
+        x = np.zeros((0, self.D), dtype=np.float32) if points is None else np.ascontiguousarray(np.asarray(points, dtype=np.float32)).reshape(-1, self.D)
+        check(lib().wl_sim_set_tracers(self._h, x.ctypes.data_as(C.POINTER(C.c_float)), int(x.shape[0])))
+
+    def tracers(self):
+        """(x, x_prev): positions and positions before the last step, as (n, D) device tensors over the handle's memory (valid until set_tracers)"""
+        import torch
+        out = []
+        for which in (0, 1):
+            n = C.c_size_t(0)
+            p = lib().wl_sim_tracers(self._h, which, C.byref(n))
+            if not p or n.value == 0:
+                out.append(torch.empty((0, self.D), dtype=torch.float32, device=core.device()))
+                continue
+            cnt, addr = int(n.value) * self.D, int(p)
+
+            class _Mem:      # __cuda_array_interface__ of memory the handle owns
+                __cuda_array_interface__ = {"shape": (cnt,), "typestr": "<f4", "data": (addr, False), "version": 2}
+            out.append(torch.as_tensor(_Mem(), device=core.device()).view(int(n.value), self.D))
+        return out[0], out[1]
 
     def sync(self):
         check(lib().wl_stream_sync(stream()))
