@@ -6,6 +6,8 @@ inside the corrector's loader; and the counter says the stores were really skipp
 import numpy as np
 import pytest
 
+from callseq import assert_same_state, bits      # u, u⁰, p on every cell as raw bits, pois.n, the Δt history
+
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
@@ -27,19 +29,6 @@ def tgv(w, dims=DIMS, **opts):
     for k, v in opts.items():
         sg.set_option(k, v)
     return sg
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def assert_same_state(a, b, what):
-    for name in ("u", "u0", "p"):
-        x, y = bits(a.field(name)), bits(b.field(name))
-        assert np.array_equal(x, y), (what, name, int((x != y).sum()))
-    assert a.pois_n == b.pois_n, (what, a.pois_n, b.pois_n)
-    da, db = [f32(v).view(np.uint32) for v in a.dt], [f32(v).view(np.uint32) for v in b.dt]
-    assert da == db, (what, [float(v) for v in a.dt], [float(v) for v in b.dt])
 
 
 def run_calls(w, sg, calls):

@@ -155,4 +155,22 @@ def test_lean_loader_other_schemes(w):
             run(on, calls)
             run(off, calls)
             assert_same_state(on, off, (lam, calls))
+            x, y = bits(on.field("sigma")), bits(off.field("sigma"))      # the stale Φ in σ's ghost cells: k_conv_q1's instance of this scheme
+            assert np.array_equal(x, y), (lam, calls, "sigma", int((x != y).sum()))
         assert on.counter("tailfuse") == 4
+
+
+def test_sigma_ghost_cells_after_a_step_are_those_of_the_separate_tail(w):
+    """the reduced sequence of a mismatch the randomised call-sequence test found (tests/test_gpu_callseq.py, box seed 2: steps(3), metric("ke") into σ): one
+    step, then σ read.  σ's upper ghost cells hold conv_diff!'s stale Φ of the corrector's advecting field (quirk Q1), and CFL's maximum(σ) sees them.  With
+    the first tail inside the corrector's loader that field is never in memory, and the small launch that leaves the stale Φ (k_conv_q1) read the array — the
+    predictor's velocity WITHOUT u −= L∇x and BC!: 4466 of σ's 9192 ghost cells differed at 64×32×24 (u, u⁰, p, pois.n and Δt were equal, the maximum being on
+    an interior cell).  Fixed in wl_flow.hip: when the tiled launch took the deferred projection (fold->proj_x), k_conv_q1 forms every operand as the loader of
+    wl_convf.hip does — U on wall-normal faces, u − c·(x[c] − x[c−δ]) at the clamped cell elsewhere.  One launch as before."""
+    on, off = make(w, DIMS, (0.3, -0.2, 0.1), 211, tailfuse=1), make(w, DIMS, (0.3, -0.2, 0.1), 211, tailfuse=0)
+    for s in (on, off):
+        s.mom_step_()
+    assert on.counter("tailfuse") == 1 and off.counter("tailfuse") == 0
+    assert_same_state(on, off, "one step")
+    x, y = bits(on.field("sigma")), bits(off.field("sigma"))
+    assert np.array_equal(x, y), int((x != y).sum())

@@ -96,6 +96,7 @@ int g_convf_on = 1;
 // — the statements of k_project_unscale (constant coefficients: L = c_a away from the wall faces) followed by BC!'s closed form for a tuple U
 // (wl_bcfold.hpp), so the values are bit for bit those the separate tail + BC! launches would have left in memory; the projected predictor
 // velocity is never written (−24 B/cell of the step's traffic and one launch).  FULL tiles, single domain, no periodic direction / exit / body.
+// (k_conv_q1<…, PROJ> in wl_flow.hip holds a second copy of this closed form for σ's stale ghost-cell fluxes: the two must stay the same expression, operand for operand.)
 template <int SCH, int FULL, int U0ADV, int MODE, int PROJ>
 __global__ void __launch_bounds__(CF_N, 4) k_conv_flux(GridX g, const float* __restrict__ u, float nu, int ka, int kb, int zchunk, BdimArgs bd) {
   __shared__ float lds[CF_LDS + (PROJ ? CF_GENC * 256 : 0)];

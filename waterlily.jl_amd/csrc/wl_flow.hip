@@ -162,8 +162,12 @@ __global__ void __launch_bounds__(WL_BLOCK, WL_CD_WAVES) k_conv_diff(GridX g, fl
 // Quirk Q1: Φ≡σ keeps the fluxes of the LAST pass that covered a cell; interior values are
 // overwritten by div/flux_out later, so only upper-ghost cells matter for CFL's maximum(σ).  Reproduced by this
 // small kernel over the three upper ghost planes (blockIdx.y = direction whose index is Ng).
-template <int D, int SCH>
-__global__ void k_conv_q1(GridX g, float* __restrict__ Phi, const float* __restrict__ u, float nu, unsigned per) {
+// PROJ (3-D, single domain, no periodic direction): the advecting field is read through mom_project!'s deferred tail and BC! as the loader of wl_convf.hip
+// reads it — u holds the unprojected predictor velocity, px the solver's x — so that the stale Φ is that of the field conv_diff! saw: per operand
+// U_a where component a is normal to a boundary face, u_a[c] − c_a·(x[c] − x[c−δa]) elsewhere, c = the cell with the two other coordinates clamped inside.
+struct Q1Proj { const float* px = nullptr; float c[3] = {0.f, 0.f, 0.f}; float U[3] = {0.f, 0.f, 0.f}; };
+template <int D, int SCH, int PROJ = 0>
+__global__ void k_conv_q1(GridX g, float* __restrict__ Phi, const float* __restrict__ u, float nu, unsigned per, Q1Proj pj) {
   const int d = blockIdx.y;
   const int N[3] = {g.nx, g.ny, (D == 3) ? g.gnz : 1};
   const long st[3] = {1, g.sy, g.sz};
@@ -190,6 +194,22 @@ __global__ void k_conv_q1(GridX g, float* __restrict__ Phi, const float* __restr
     const bool covered = zin || (I[b] >= 3 && I[b] <= N[b] - 1) || (pb && I[b] == 2);
     if (!covered) continue;
     const float* __restrict__ ub = u + (long)b * g.cs;
+    if (PROJ && D == 3) {      // flux_inner (b is never periodic here) on operands formed on load; every load goes to an interior cell
+      auto val = [&](int c, int X, int Y, int Z) -> float {
+        const int ic = c == 0 ? X : (c == 1 ? Y : Z);
+        if (ic <= 1 || ic >= N[c] - 1) return pj.U[c];
+        const int Xc = c == 0 ? X : (X < 1 ? 1 : (X > g.nx - 2 ? g.nx - 2 : X)), Yc = c == 1 ? Y : (Y < 1 ? 1 : (Y > g.ny - 2 ? g.ny - 2 : Y));
+        const int Zc = c == 2 ? Z : (Z < 1 ? 1 : (Z > g.nz - 2 ? g.nz - 2 : Z));
+        const long oc = (long)Xc + (long)Yc * g.sy + (long)Zc * g.sz;
+        return u[(long)c * g.cs + oc] - pj.c[c] * (pj.px[oc] - pj.px[oc - st[c]]);
+      };
+      auto fa = [&](int k) -> float { return val(a, loc[0] + (b == 0 ? k : 0), loc[1] + (b == 1 ? k : 0), loc[2] + (b == 2 ? k : 0)); };
+      const float U = (val(b, loc[0], loc[1], loc[2]) + val(b, loc[0], loc[1], loc[2] - 1)) / 2;
+      const float fm2 = fa(-2), fm1 = fa(-1), f0 = fa(0), fp1 = fa(1);
+      const float conv = U > 0 ? U * lam<SCH>(fm2, fm1, f0) : U * lam<SCH>(fp1, f0, fm1);
+      Phi[o] = conv - nu * (f0 - fm1);
+      break;
+    }
     Phi[o] = (I[b] == 2 && !zin) ? flux_lowerP<SCH>(f, ub, o, st[b], st[a], nu, o + (long)(N[b] - 4) * st[b]) : flux_inner<SCH>(f, ub, o, st[b], st[a], nu);
     break;
   }
@@ -698,7 +718,7 @@ static int conv_diff_launch2(float* r, const float* u, float* Phi, const GridX& 
       long cmax = (long)g.ny * (D == 3 ? g.nz : 1);
       cmax = cmax > (long)g.nx * (D == 3 ? g.nz : 1) ? cmax : (long)g.nx * (D == 3 ? g.nz : 1);
       cmax = cmax > g.sz ? cmax : g.sz;
-      hipLaunchKernelGGL((k_conv_q1<D, SCH>), dim3((unsigned)((cmax + WL_BLOCK - 1) / WL_BLOCK), (unsigned)D, 1), dim3(WL_BLOCK), 0, s, g, Phi, u, nu, per);
+      hipLaunchKernelGGL((k_conv_q1<D, SCH>), dim3((unsigned)((cmax + WL_BLOCK - 1) / WL_BLOCK), (unsigned)D, 1), dim3(WL_BLOCK), 0, s, g, Phi, u, nu, per, Q1Proj{});
       WL_LAUNCH_CHECK();
     }
     return 0;
@@ -739,7 +759,12 @@ static int conv_diff_launch2(float* r, const float* u, float* Phi, const GridX& 
     long cmax = (long)g.ny * (D == 3 ? g.nz : 1);
     cmax = cmax > (long)g.nx * (D == 3 ? g.nz : 1) ? cmax : (long)g.nx * (D == 3 ? g.nz : 1);
     cmax = cmax > g.sz ? cmax : g.sz;
-    hipLaunchKernelGGL((k_conv_q1<D, SCH>), dim3((unsigned)((cmax + WL_BLOCK - 1) / WL_BLOCK), (unsigned)D, 1), dim3(WL_BLOCK), 0, s, g, Phi, u, nu, per);
+    if (D == 3 && tiled && fold && fold->proj_x) {      // the tiled launch read u through the deferred projection: so does this one
+      Q1Proj pj; pj.px = fold->proj_x;
+      for (int c = 0; c < 3; c++) { pj.c[c] = bd->cl_c[c]; pj.U[c] = fold->U[c]; }
+      hipLaunchKernelGGL((k_conv_q1<D, SCH, 1>), dim3((unsigned)((cmax + WL_BLOCK - 1) / WL_BLOCK), (unsigned)D, 1), dim3(WL_BLOCK), 0, s, g, Phi, u, nu, per, pj);
+    } else
+    hipLaunchKernelGGL((k_conv_q1<D, SCH>), dim3((unsigned)((cmax + WL_BLOCK - 1) / WL_BLOCK), (unsigned)D, 1), dim3(WL_BLOCK), 0, s, g, Phi, u, nu, per, Q1Proj{});
   }
   WL_LAUNCH_CHECK(); return 0;
 }
@@ -764,7 +789,7 @@ int conv_q1(float* Phi, const float* u, const GridX& g, float nu, unsigned per, 
   cmax = cmax > (long)g.nx * (g.D == 3 ? g.nz : 1) ? cmax : (long)g.nx * (g.D == 3 ? g.nz : 1);
   cmax = cmax > g.sz ? cmax : g.sz;
   const dim3 grid((unsigned)((cmax + WL_BLOCK - 1) / WL_BLOCK), (unsigned)g.D, 1);
-#define WL_Q1(DD, SCHV) hipLaunchKernelGGL((k_conv_q1<DD, SCHV>), grid, dim3(WL_BLOCK), 0, s, g, Phi, u, nu, per)
+#define WL_Q1(DD, SCHV) hipLaunchKernelGGL((k_conv_q1<DD, SCHV>), grid, dim3(WL_BLOCK), 0, s, g, Phi, u, nu, per, Q1Proj{})
   if (g.D == 3) { if (scheme == WL_QUICK) WL_Q1(3, WL_QUICK); else if (scheme == WL_VANLEER) WL_Q1(3, WL_VANLEER); else WL_Q1(3, WL_CDS); }
   else { if (scheme == WL_QUICK) WL_Q1(2, WL_QUICK); else if (scheme == WL_VANLEER) WL_Q1(2, WL_VANLEER); else WL_Q1(2, WL_CDS); }
 #undef WL_Q1
