@@ -1,5 +1,5 @@
 """NumPy restatement of what decides the body-aware fast paths (csrc/wl_flow.hip k_body_mask2, body_masks_box, body_masks_planes,
-conv_diff_bdim_body; csrc/wl_capi.hip wl_mg::update): from host copies of μ₀, μ₁, V (ghost cells included, as FusedSimulation.field
+conv_diff_bdim_body; csrc/wl_mg.hip wl_mg::update, wl_mg::zsplit_ranges): from host copies of μ₀, μ₁, V (ghost cells included, as FusedSimulation.field
 returns them) the three masks per (plane, workgroup of 256 consecutive in-plane cells), the two host scans, the census the library
 reports through wl_sim_counter("mask_*"), and the plane ranges the tiled conv_diff! and the z-split smoother take.  Test infrastructure."""
 import numpy as np

@@ -171,7 +171,34 @@ __device__ __forceinline__ float block_max(float v) {
 struct RedWs {
   double* pa; double* pb; float* pm; double* res_d; float* res_f;
 };
-static inline size_t wl_red_bytes() { return (size_t)WL_MAXPART * (8 + 8 + 4) + 8 * 8 + 8 * 4 + 64; }
+// The result slots, one line each: who writes -> who reads.  Two users of one slot never run inside the same solve (said where it happens).
+enum WlResD : int {
+  WL_RD_SUM = 0,      // Σr: residual!'s k_final_sum, the fused head (k_resjac_fin) -> k_mean_shift, k_shift_norms, the shifting Jacobi!, k_decide, solve's first read.
+                      //   Also THE result of a leaf reduction (wl_sum, wl_dot, wl_L2_inside, pcg_stage) and metrics_stats_dev's Σke: leaves run between solves, never inside one
+  WL_RD_SUM2 = 1,     // metrics_stats_dev's Σ½|ω|² (a leaf, as above) …
+  WL_RD_L1_INIT = 1,  // … and L₁ of the initial residual: shift_norms_dev, the shifting Jacobi!, the fused head -> solve's first read (the ω rule), wl_poisson_solve's L₁
+  WL_RD_L1 = 2,       // L₁ of the new residual: kernel B / norms_dev -> k_decide, solve (z-split: plane range 0)
+  WL_RD_EXIT = 4,     // exitBC!'s two face means, slots 4 and 5: k_exit_facesum* -> k_exit_mean / k_exit_update (between the solves of a step)
+  WL_RD_FORCE = 4,    // a force or moment sum, slots 4, 5, 6: k_fin3 -> the host (a read-out between steps: no solve, no exitBC! in flight)
+  WL_RD_L1_Z1 = 5,    // z-split smoother, plane ranges 1 and 2: kernel B -> solve.  Shares slot 5 with exitBC!'s second mean: exitBC! runs before
+  WL_RD_L1_Z2 = 6,    //   the first projection of a step and has consumed its means (k_exit_update) before the solver's first kernel B
+  WL_RD_COUNT = 8
+};
+enum WlResF : int {
+  WL_RF_LEAF = 0,       // THE result of a leaf reduction (wl_max, wl_norms, wl_cfl, metrics_stats_dev's max|ω|): between solves …
+  WL_RF_LINF_INIT = 0,  // … and L∞ of the initial residual: shift_norms_dev, the shifting Jacobi!, the fused head -> solve's first read (the log)
+  WL_RF_LINF = 1,       // L∞ of the new residual: kernel B / norms_dev -> k_decide, solve (z-split: plane range 0)
+  WL_RF_LINF_Z1 = 2,    // z-split smoother, plane ranges 1 and 2: kernel B -> solve
+  WL_RF_LINF_Z2 = 3,
+  WL_RF_GO = 4,         // k_decide's flag (1 converged / 0 iterate / −1 the head's mean shift is due) -> solve, and the gated projection tail's `go`
+  WL_RF_CFL = 5,        // CFL's maximum: cfl_dev, the pair tail -> k_dt_from_cfl, the host (not slot 0: a tail queued ahead of the solver's read must leave the head's L∞ there for the log)
+  WL_RF_DT = 6,         // Δt of the next step: k_dt_from_cfl -> the predictor queued behind it
+  WL_RF_IFLAG = 7,      // an `int` flag: scratch of check_const_L, shell_nonzero and update!'s slab agreement, each read back before anything else is queued
+  WL_RF_COUNT = 8
+};
+constexpr int wl_upto(int slot) { return slot + 1; }      // read_results' counts: "up to and including slot X"
+static_assert(WL_RD_COUNT * sizeof(double) == 64 && WL_RF_COUNT * sizeof(float) <= 64, "res_f starts 64 bytes behind res_d (wl_red_ws, the pinned 128-byte record of WlCtx)");
+static inline size_t wl_red_bytes() { return (size_t)WL_MAXPART * (8 + 8 + 4) + WL_RD_COUNT * sizeof(double) + WL_RF_COUNT * sizeof(float) + 64; }
 static inline RedWs wl_red_ws(void* base) {
   RedWs w; char* b = (char*)base;
   w.pa = (double*)b; w.pb = (double*)(b + (size_t)WL_MAXPART * 8); w.pm = (float*)(b + (size_t)WL_MAXPART * 16);

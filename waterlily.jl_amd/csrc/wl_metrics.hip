@@ -276,7 +276,7 @@ __global__ void __launch_bounds__(WL_BLOCK) k_stats_final(const double* __restri
   double a = 0.0, b = 0.0; float mx = 0.f;
   for (int q = threadIdx.x; q < n; q += WL_BLOCK) { a += pa[q]; b += pb[q]; mx = fmaxf(mx, pm[q]); }
   a = block_sum(a); b = block_sum(b); mx = block_max(mx);
-  if (threadIdx.x == 0) { res_d[0] = a; res_d[1] = b; res_f[0] = mx; }
+  if (threadIdx.x == 0) { res_d[WL_RD_SUM] = a; res_d[WL_RD_SUM2] = b; res_f[WL_RF_LEAF] = mx; }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------

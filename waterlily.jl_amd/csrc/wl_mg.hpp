@@ -1,9 +1,15 @@
 // MultiLevelPoisson handle (struct src/MultiLevelPoisson.jl:61-77) — internal C++ definition behind `wl_mg`.
 #pragma once
+#include <algorithm>
 #include <functional>
 #include <vector>
 
 #include "wl_comm.hpp"
+
+bool wl_mg_divisible(int n);      // divisible(N)  src/MultiLevelPoisson.jl:52
+// result slots of the z-split smoother's plane ranges: written by smooth!'s kernel B, summed by solver!
+struct WlNormSlots { int d, f; };
+inline constexpr WlNormSlots WL_ZS_NORMS[3] = {{WL_RD_L1, WL_RF_LINF}, {WL_RD_L1_Z1, WL_RF_LINF_Z1}, {WL_RD_L1_Z2, WL_RF_LINF_Z2}};
 
 struct wl_mg {
   struct Level {            // one `Poisson` (src/Poisson.jl:22-39)
@@ -50,17 +56,21 @@ struct wl_mg {
   bool shift_pending = false;
   bool deep_halo = true;     // z-slabs with >= 5 ghost planes: one r exchange (5 planes) per smooth! instead of r (2) + ϵ_mid (3) + r' (2)
   // One-shot hook of the next solve(): the projection tail, queued behind every iteration's smoother BEFORE the host reads that iteration's norms and gated on the
-  // device by the break test (wl::decide_converged → res_f[4], also the host's decision): no idle GPU while the host decides, nothing happens if the loop goes on.
-  // spec_check_head: 1 — the flag of the first iteration first carries the fused head's mean-shift test (wl_sim's early V-cycle), 2 — declares that shift due
+  // device by the break test (wl::decide_converged → res_f[WL_RF_GO], also the host's decision): no idle GPU while the host decides, nothing happens if the loop goes on.
+  // check_head: 1 — the flag of the first iteration first carries the fused head's mean-shift test (wl_sim's early V-cycle), 2 — declares that shift due
   // (test hook).  Results: tail_stood — the tail ran; head_decided — the device took the head's decision, head_due — and found the shift due (the loop stopped
   // after that iteration: the caller discards the solve).
-  std::function<int(const float*)> spec_tail; int spec_check_head = 0; bool tail_stood = false, head_decided = false, head_due = false;
+  struct Spec {
+    std::function<int(const float*)> tail; int check_head = 0; bool tail_stood = false, head_decided = false, head_due = false;
+    void disarm() { tail = nullptr; check_head = 0; }
+    void begin_solve(std::function<int(const float*)>* t, int* check) { t->swap(tail); *check = check_head; disarm(); tail_stood = head_decided = head_due = false; }   // the one place that resets it
+  } spec;
   int shift_path = -1;      // how the last solve applied residual!'s mean shift (src/Poisson.jl:95-97): 0 its own pass (k_shift_norms), 1 inside the finest level's
                             // z-marching Jacobi! (deferred), 2 left to the caller (the fused projection head); −1 no solve yet
   hipStream_t side = nullptr; hipEvent_t ev_decided = nullptr;   // the host waits for the copy of such an iteration's norms (this event), not for the tail queued behind it
   double first_hd0 = 0.0;   // res_d[0] as the first iteration's read found it (the fused head's Σr when its check is deferred: wl_sim)
   bool jacobi0_done = false; // the fused projection head (wl_resjac.hip) already ran the V-cycle's first Jacobi! on the finest level and left solver!'s first norms
-  int norm_slots = 0;       // z-split smoother: which plane ranges left an (L₁, L∞) pair in their own result slots
+  int norm_slots = 0;       // z-split smoother: which plane ranges left an (L₁, L∞) pair in their own result slots (WL_ZS_NORMS)
   bool par_ranges = false;  // levels with a body: the plane ranges of the z-split on concurrent streams (wl::par_fork / par_join) — measured SLOWER (sphere 256³ 2.84 -> 3.07 ms: the fork/join events cost more than the overlap of 35–76 µs launches returns); "zsplit_par" turns it on
   int x_halo_depth = 1;     // z-slabs: ghost planes of x refreshed at the end of solver! (the projection tail reads 1; the fused projection head of the NEXT solve reads 2)
   int last_xdefer = -1;     // what the finest level's last smooth! with a pending prolongation decided: 1 = x += ω·x_c↓ deferred to kernel B, 0 = applied by kernel A (−1: none yet)
@@ -78,6 +88,55 @@ struct wl_mg {
   int halo(Level& v, float* a, int ncomp, hipStream_t s, int depth = 1, bool wrap = true) { return v.dist ? wl::halo(comm, a, v.x_, ncomp, depth, s, wrap) : 0; }
   // a distributed level whose smooth! runs as the blocked pair kernels (constant coefficients, 3 ghost planes)
   bool pair_slab(const Level& v) const { return v.dist && v.g.k0 >= 3 && use_fused && !perdir && wl::gsrb_pair_ok(v.x_, v.cl); }
+  // ---- the predicates the stages of the V-cycle share, each stated once (DESIGN §4.3c lists their users)
+  // smooth!(it = 4) of this level runs as kernel A + kernel B (and absorbs a deferred prolongation)
+  bool blocked(const Level& v) const { return use_fused && (wl::gsrb_fused_ok(v.x_, perdir, v.dist) || pair_slab(v)); }
+  // z-slab with >= 5 ghost planes: one five-plane exchange of r per smooth! — kernel A starts five planes out
+  bool deep_slab(const Level& v) const { return v.dist && deep_halo && v.g.k0 >= 5 && v.g.k1 - v.g.k0 >= 5; }
+  // ghost planes of coarse.x the prolongation into `fine` reads: the coarse cells under the planes kernel A of fine's smooth! starts on
+  int coarse_x_depth(const Level& fine, const Level& coarse) const {
+    if (!(fine.dist && blocked(fine))) return 1;
+    return deep_slab(fine) && coarse.g.k0 >= 3 && coarse.g.k1 - coarse.g.k0 >= 3 ? 3 : 2;
+  }
+  // a level with a body: planes [na, nb) around it take the general-coefficient kernels, [k0, na) and [nb, k1) the constant-coefficient ones.
+  // na, nb follow za, zb whether or not the split is on (update! decides `part` from them)
+  static constexpr int ZSPLIT_MARGIN = 4;      // planes between the body's last deviating plane and the first constant-coefficient one: the reach of one smooth!
+  struct ZRanges { bool on; int na, nb; };
+  ZRanges zsplit_ranges(const Level& v) const { return {v.part && use_zsplit && !v.dist, std::max(v.g.k0, v.za - ZSPLIT_MARGIN), std::min(v.g.k1, v.zb + ZSPLIT_MARGIN + 1)}; }
+  // kernel B of this launch may leave r' unstored (wl::B_XONLY; see skip_r)
+  bool b_xonly_ok(const Level& p, int bout, bool want_norms) const {
+    return bout == wl::B_XONLY && skip_r && !store_eps && !comm && !p.dist && !p.part && !perdir && wl::gsrb_pair_B_ok(nullptr, p.r, p.x, p.em, p.rs, p.x_, p.cl) &&
+           (!want_norms || wl::gsrb_pair_B_kernel_norms(p.x_));
+  }
+  // ---- smooth! in forms: decided once per call (plan_smooth), one function per form, one epilogue (smooth)
+  //   Passes           gs_init (+ sweep 1), one kernel per further sweep, increment!; a pending prolongation is flushed first
+  //   Blocked          kernel A, kernel B; z-slabs: r (2 planes) before A, ϵ_mid (3) [+ r' (2)] before B
+  //   DeepSlab         z-slab with a pending prolongation and >= 5 ghost planes: r five planes deep, then A on the extended range, then B
+  //   DeepSlabOverlap  … that exchange in flight while A computes the interior planes; the two boundary slices follow the wait
+  //   ZSplit           Blocked on the three plane ranges of zsplit_ranges, each with its own coefficients and result slots
+  enum class Smooth { Passes, Blocked, DeepSlab, DeepSlabOverlap, ZSplit };
+  struct SmoothPlan {
+    Smooth form; bool pro;      // pro: the level's pending prolongate!+increment! runs as a stage of kernel A (every form but Passes)
+    bool xdefer;                // … and its `x += ω·x_c↓` is handed on to kernel B (wl::XDefer); ZSplit decides per range and reports the last range's
+    int bout;                   // wl::BOut of kernel B
+    bool want_norms;
+  };
+  SmoothPlan plan_smooth(const Level& p, int it, bool want_norms, int bout) const;
+  int smooth_passes(Level& p, int l, int it, float w, hipStream_t s);
+  int smooth_blocked(Level& p, Level* coarse, int l, float w, const SmoothPlan& plan, hipStream_t s);
+  int smooth_deep_slab(Level& p, Level& coarse, int l, float w, const SmoothPlan& plan, hipStream_t s);
+  int smooth_zsplit(Level& p, Level* coarse, int l, float w, SmoothPlan* plan, hipStream_t s);
+  int exchange_for_B(Level& p, bool with_rs, hipStream_t s);
+  // ---- Vcycle! in stages
+  int jacobi_fine(int l, hipStream_t s);
+  int restrict_to_coarse(int l, bool to_tail, hipStream_t s);
+  int descend(int l, bool to_tail, float w, hipStream_t s);
+  int prolong(int l, float w, bool defer, hipStream_t s);
+  // ---- solver! in stages
+  struct SolveRun;
+  int initial_residual(int itmx, bool have_residual, bool head_read, hipStream_t s);
+  int iteration(SolveRun& st, hipStream_t s);
+  void apply_norms(SolveRun& st);
   ~wl_mg();
   int update(hipStream_t s);
   int smooth(int l, int it, float w, hipStream_t s, bool want_norms = false, bool* norms_done = nullptr, int bout = 0);   // bout = wl::B_XONLY: r' need not be stored (honoured where skip_r acts)

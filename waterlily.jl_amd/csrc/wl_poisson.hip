@@ -1229,7 +1229,7 @@ int residual_part(float* r, const float* x, const float* z, const float* L, cons
   const int np = g.k1 - g.k0;
   dim3 grid = wl_plane_grid(g, wl_red_slots(g, np));
   DSEL(g.D, k_residual, grid, dim3(WL_BLOCK), 0, s, g, r, x, z, L, Dg, iD, ws.pa);
-  hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(WL_BLOCK), 0, s, ws.pa, (int)grid.x, ws.res_d + 0);
+  hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(WL_BLOCK), 0, s, ws.pa, (int)grid.x, ws.res_d + WL_RD_SUM);
   WL_LAUNCH_CHECK(); return 0;
 }
 #define DSEL2(D, CLF, KERN, ...)                                                                                     \
@@ -1239,7 +1239,7 @@ int div_residual(float* z, float* xout, float* r, const float* x, const float* u
   const int zc = wl_march_chunk(g, g.nz);
   dim3 grid = wl_plane_grid(g, wl_march_slots(g.nz, zc));
   DSEL2(g.D, cl.on, k_div_residual, grid, dim3(WL_BLOCK), 0, s, g, z, xout, r, x, u, L, Dg, iD, dt, ws.pa, cl, zc, 0, g.nz);
-  hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(WL_BLOCK), 0, s, ws.pa, (int)grid.x, ws.res_d + 0);
+  hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(WL_BLOCK), 0, s, ws.pa, (int)grid.x, ws.res_d + WL_RD_SUM);
   WL_LAUNCH_CHECK(); return 0;
 }
 // The same on a level with a body: the local planes [0,na) and [nb,nz) follow the constant-coefficient pattern `far` (coefficients from
@@ -1258,7 +1258,7 @@ int div_residual_split(float* z, float* xout, float* r, const float* x, const fl
     DSEL2(g.D, cl.on, k_div_residual, grid, dim3(WL_BLOCK), 0, s, g, z, xout, r, x, u, L, Dg, iD, dt, ws.pa + off, cl, zc, lo[q], hi[q]);
     off += (int)grid.x;
   }
-  hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(WL_BLOCK), 0, s, ws.pa, off, ws.res_d + 0);
+  hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(WL_BLOCK), 0, s, ws.pa, off, ws.res_d + WL_RD_SUM);
   WL_LAUNCH_CHECK(); return 0;
 }
 // Block order of the projection tails (experiments: WL_TAIL_LIN / WL_TAIL_PAIR in a -DWL_EXPERIMENTS build; profiles/r03_experiments.md §4, §8):
@@ -1317,7 +1317,7 @@ int project_unscale_split(float* u, const float* L, const float* x, float* pout,
 __global__ void k_decide(const double* __restrict__ res_d, float* __restrict__ res_f, double r1tol, double rinftol, double ninside, int check_head, int slot_d, int slot_f, int out_slot) {
   const float rnew = (float)res_d[slot_d], rinf = res_f[slot_f];
   const bool ok = (double)rnew < r1tol && (double)rinf < rinftol;
-  const bool head_due = check_head == 2 || (check_head == 1 && wl_shift_due(res_d[0], ninside));
+  const bool head_due = check_head == 2 || (check_head == 1 && wl_shift_due(res_d[WL_RD_SUM], ninside));
   res_f[out_slot] = head_due ? -1.f : (ok ? 1.f : 0.f);
 }
 int decide_converged(const RedWs& ws, double r1tol, double rinftol, double ninside, int check_head, int slot_d, int slot_f, int out_slot, hipStream_t s) {
@@ -1435,7 +1435,7 @@ int const_plane_range(const float* L, const GridX& g, const float* c, int* za, i
   return 0;
 }
 int mean_shift(float* r, const GridX& g, const RedWs& ws, hipStream_t s) {
-  hipLaunchKernelGGL(k_mean_shift, wl_plane_grid(g, g.k1 - g.k0), dim3(WL_BLOCK), 0, s, g, r, ws.res_d + 0, (double)wl_ninside_global(wl_grid{g.D, g.nx, g.ny, g.nz, g.k0, g.k1, g.gk, g.gnz}));
+  hipLaunchKernelGGL(k_mean_shift, wl_plane_grid(g, g.k1 - g.k0), dim3(WL_BLOCK), 0, s, g, r, ws.res_d + WL_RD_SUM, (double)wl_ninside_global(wl_grid{g.D, g.nx, g.ny, g.nz, g.k0, g.k1, g.gk, g.gnz}));
   WL_LAUNCH_CHECK(); return 0;
 }
 int residual(float* r, const float* x, const float* z, const float* L, const float* Dg, const float* iD, const GridX& g, const RedWs& ws, hipStream_t s) {
@@ -1481,7 +1481,7 @@ int jacobi_pp_shift(float* rout, const float* r, float* x, const GridX& g, float
   const int zc = wl_march_chunk(g, g.k1 - g.k0);
   dim3 grid = wl_plane_grid(g, wl_march_slots(g.k1 - g.k0, zc));
   const double ni = (double)wl_ninside_global(wl_grid{g.D, g.nx, g.ny, g.nz, g.k0, g.k1, g.gk, g.gnz});
-  hipLaunchKernelGGL(k_jacobi_march_cl<1>, grid, dim3(WL_BLOCK), 0, s, g, rout, r, x, w, cl, zc, (const double*)(ws.res_d + 0), ni, ws.pa, ws.pm, 0);
+  hipLaunchKernelGGL(k_jacobi_march_cl<1>, grid, dim3(WL_BLOCK), 0, s, g, rout, r, x, w, cl, zc, (const double*)(ws.res_d + WL_RD_SUM), ni, ws.pa, ws.pm, 0);
   hipLaunchKernelGGL(k_final_sum_max, dim3(1), dim3(WL_BLOCK), 0, s, ws.pa, ws.pm, (int)grid.x, ws.res_d + slot_d, ws.res_f + slot_f);
   WL_LAUNCH_CHECK(); return 0;
 }
@@ -1535,13 +1535,13 @@ int pcg_stage(int stage, float* eps, float* r, float* x, float* z, const float* 
                         else hipLaunchKernelGGL((k_pcg<2, ST>), grid, dim3(WL_BLOCK), 0, s, g, eps, r, x, z, L, Dg, iD, a, more, ws.pa); } while (0)
   switch (stage) { case 0: WL_PCG(0); break; case 1: WL_PCG(1); break; case 2: WL_PCG(2); break; default: WL_PCG(3); }
 #undef WL_PCG
-  if (stage != 3 && !(stage == 2 && !more)) hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(WL_BLOCK), 0, s, ws.pa, (int)grid.x, ws.res_d + 0);
+  if (stage != 3 && !(stage == 2 && !more)) hipLaunchKernelGGL(k_final_sum, dim3(1), dim3(WL_BLOCK), 0, s, ws.pa, (int)grid.x, ws.res_d + WL_RD_SUM);
   WL_LAUNCH_CHECK(); return 0;
 }
 int shift_norms_dev(float* r, const GridX& g, const RedWs& ws, int slot_d, int slot_f, hipStream_t s) {
   dim3 grid = wl_plane_grid(g, wl_red_slots(g, g.k1 - g.k0));
   const double ni = (double)wl_ninside_global(wl_grid{g.D, g.nx, g.ny, g.nz, g.k0, g.k1, g.gk, g.gnz});
-  hipLaunchKernelGGL(k_shift_norms, grid, dim3(WL_BLOCK), 0, s, g, r, ws.res_d + 0, ni, ws.pa, ws.pm);
+  hipLaunchKernelGGL(k_shift_norms, grid, dim3(WL_BLOCK), 0, s, g, r, ws.res_d + WL_RD_SUM, ni, ws.pa, ws.pm);
   hipLaunchKernelGGL(k_final_sum_max, dim3(1), dim3(WL_BLOCK), 0, s, ws.pa, ws.pm, (int)grid.x, ws.res_d + slot_d, ws.res_f + slot_f);
   WL_LAUNCH_CHECK(); return 0;
 }

@@ -97,7 +97,7 @@ __global__ void k_resjac_fin(const double* __restrict__ psum, const double* __re
   if (threadIdx.x == 0) {
     a = 0.0; l = 0.0; mx = 0.f;
     for (int q = 0; q < WL_BLOCK / 64; q++) { a += sa[q]; l += sl[q]; mx = fmaxf(mx, sm[q]); }
-    res_d[0] = a; res_d[slot_d] = l; res_f[slot_f] = mx;
+    res_d[WL_RD_SUM] = a; res_d[slot_d] = l; res_f[slot_f] = mx;
   }
 }
 }  // namespace

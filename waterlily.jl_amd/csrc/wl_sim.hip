@@ -283,7 +283,7 @@ struct wl_sim {
     const float* proj_pending = nullptr;   // the tail left to the corrector's loader: u still lacks −L∇x of this x -> conv_fused, inside the same step (it fails the step otherwise); never outlives mom_step
     float p_scale_pending = 0.f;     // a tail that skipped its store ("pdefer"): ≠ 0, p holds the solver's scaled x, the pressure is p / p_scale_pending -> the next fused head divides on load; materialise_p
     bool dt_pending = false;         // cfl(more_follow): Δt of the next step is on the device only -> the next mom_step of the same call reads it back behind its predictor; never outlives wl_sim_mom_steps
-    bool cfl_done = false;           // the pair tail: max σ is already in CFL_SLOT -> cfl(), which then launches nothing; nothing to settle
+    bool cfl_done = false;           // the pair tail: max σ is already in WL_RF_CFL -> cfl(), which then launches nothing; nothing to settle
   } df;
   // makes memory current for a reader outside the step (fields handed out, force read-outs, wl_sim_phase, a failed step).  Between calls nothing is pending but, on
   // slabs, the exchange — "a call never returns with the divisor pending", every projection ends with BC! applied — so this launches nothing there.
@@ -484,7 +484,6 @@ struct wl_sim {
   bool resjac_backoff = false;            // (a flow whose residual needs the mean shift on every solve would pay launch + sync + two-kernel path each time); re-armed by update!
   int p_shell = -1;          // ghost shell of p / the spare pressure array: -1 unknown (check before the next fused head), 0 all +0, 1 something else, 2 caller-owned p (never assumed)
   bool use_fuse_cfl = true;  // the corrector's projection tail also produces CFL's σ and max(σ)
-  static constexpr int CFL_SLOT = 5;   // res_f slot of CFL's maximum (not slot 0: a tail queued ahead of the solver's read must leave the head's L∞ there for the log)
   bool use_tailspec = true;  // the projection tail is queued behind the smoother before the host has read the norms, gated on the device by the break test (single GPU)
   long n_tailspec = 0, n_tailspec_armed = 0;   // projection tails that ran gated / solves the gated tail was armed for (the difference: withheld — capped, or the head redone)
   // p = x/Δt NOT STORED between the solves of a time step (option "pdefer", wl_pdefer.hpp, df.p_scale_pending).  The unscaled pressure a projection tail writes has
@@ -522,8 +521,8 @@ struct wl_sim {
   };
   struct ZSplit { bool on; int na, nb; };      // a body: the plane range [na, nb) around it takes the general-coefficient kernels, the ranges below and above the constant-coefficient ones (as in smooth!)
   ZSplit zsplit() const {
-    const wl_mg::Level& l0 = mg->lv[0]; const int zm = 4; const bool on = l0.part && mg->use_zsplit && !comm;
-    return {on, on ? std::max(l0.g.k0, l0.za - zm) : 0, on ? std::min(l0.g.k1, l0.zb + zm + 1) : 0};
+    const wl_mg::ZRanges z = mg->zsplit_ranges(mg->lv[0]);      // the smoother's ranges; a slab handle runs the whole-level forms
+    return {z.on && !comm, z.na, z.nb};
   }
   // the tail's form, decided once per projection (before the head: it reads df.bc_deferred as the head will find it)
   //   PairCfl        u −= L∇x, flux_out and its maximum into the spare velocity array (the pair kernels; with a body: their z-split form)
@@ -554,11 +553,11 @@ struct wl_sim {
     fr.wide = use_tailwide ? 1 : 0; fr.wide_ran = &done->wide;
     switch (plan.form) {
       case Tail::PairCfl:
-        if (plan.z.on) { WL_TRY(flush_bc(s)); WL_TRY(wl::project_cfl_split(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, l0.clp, plan.z.na, plan.z.nb, mg->ws, CFL_SLOT, s, store_f ? 1 : 0)); break; }
+        if (plan.z.on) { WL_TRY(flush_bc(s)); WL_TRY(wl::project_cfl_split(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, l0.clp, plan.z.na, plan.z.nb, mg->ws, WL_RF_CFL, s, store_f ? 1 : 0)); break; }
         if (df.bc_deferred && !(fr.on && wl::project_cfl_pair_path(G, l0.cl))) WL_TRY(flush_bc(s));
         fr.usub = df.bc_deferred ? 1 : 0;      // flux_out reads the wall-normal boundary faces of the corrector's output: U on load
         done->skips_p = wl::project_cfl_pair_path(G, l0.cl) && skip_p_now(c);
-        WL_TRY(wl::project_cfl(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, mg->ws, CFL_SLOT, s, store_f ? 1 : 0, &fr, done->skips_p)); df.bc_folded = fr.on != 0;
+        WL_TRY(wl::project_cfl(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, mg->ws, WL_RF_CFL, s, store_f ? 1 : 0, &fr, done->skips_p)); df.bc_folded = fr.on != 0;
         break;
       case Tail::SplitInPlace: WL_TRY(wl::project_unscale_split(u, mu0, p, ps, G, dtl, l0.cl, l0.clp, plan.z.na, plan.z.nb, s)); break;
       case Tail::Loader:        // (with the store skipped this tail launches nothing at all: the corrector's head takes x with the pending divisor)
@@ -592,24 +591,24 @@ struct wl_sim {
   int head_speculate(const ProjCall& c, float dtl, const TailPlan& plan, TailDone* done, Head* h, hipStream_t s) {
     head_take(h);
     // armed: the device decides whether the head stands (k_decide: −1 = shift due; the resjac=2/3 hook declares it due there too), the host reads that flag
-    struct SpecClear { wl_mg* m; ~SpecClear() { m->spec_tail = nullptr; m->spec_check_head = 0; } } spec_clear{mg};   // the hook captures this frame: never outlives it
+    struct SpecClear { wl_mg* m; ~SpecClear() { m->spec.disarm(); } } spec_clear{mg};   // the hook captures this frame: never outlives it
     if (use_tailspec && plan.gateable) {
-      mg->spec_tail = [&, dtl, done, s](const float* go) { return launch_tail(plan, c, dtl, go, done, s); };
-      mg->spec_check_head = resjac_force_redo ? 2 : 1; n_tailspec_armed++;
+      mg->spec.tail = [&, dtl, done, s](const float* go) { return launch_tail(plan, c, dtl, go, done, s); };
+      mg->spec.check_head = resjac_force_redo ? 2 : 1; n_tailspec_armed++;
     }
     const int slot = mg->rskip_slot, hist = slot >= 0 ? mg->rskip_hist[slot] : 0;
     WL_TRY(mg->solve(2e-3, itmx, nullptr, nullptr, nullptr, s, true, nullptr, nullptr));
-    h->tail_ran = mg->tail_stood; if (h->tail_ran) n_tailspec++;
-    const bool due = mg->head_decided ? mg->head_due : (resjac_force_redo || wl_shift_due(mg->first_hd0, (double)wl_ninside_global(mg->lv[0].g)));
+    h->tail_ran = mg->spec.tail_stood; if (h->tail_ran) n_tailspec++;
+    const bool due = mg->spec.head_decided ? mg->spec.head_due : (resjac_force_redo || wl_shift_due(mg->first_hd0, (double)wl_ninside_global(mg->lv[0].g)));
     if (due) { head_discard(h); if (slot >= 0) mg->rskip_hist[slot] = hist; }      // (a discarded solve is nobody's "rskip" history)
     else { head_accept(h); h->solved = true; }
     return 0;
   }
   int head_read_back(Head* h, hipStream_t s) {
     WL_TRY(wl::combine_results(comm, mg->ws, s));            // z-slabs: Σr, L₁ (sums) and L∞ (max) over the ranks — every rank takes the same branch below
-    double hd2[2]; WL_TRY(wl::read_results(mg->ws, hd2, 2, &h->pre_rinf, 1, s));
-    h->pre_r1 = hd2[1];
-    if (!wl_shift_due(hd2[0], (double)wl_ninside_global(mg->lv[0].g)) && !resjac_force_redo) head_accept(h);
+    double hd[WL_RD_COUNT]; float hf[WL_RF_COUNT]; WL_TRY(wl::read_results(mg->ws, hd, wl_upto(WL_RD_L1_INIT), hf, wl_upto(WL_RF_LINF_INIT), s));
+    h->pre_r1 = hd[WL_RD_L1_INIT]; h->pre_rinf = hf[WL_RF_LINF_INIT];
+    if (!wl_shift_due(hd[WL_RD_SUM], (double)wl_ninside_global(mg->lv[0].g)) && !resjac_force_redo) head_accept(h);
     else head_discard(h);
     return 0;
   }
@@ -618,8 +617,8 @@ struct wl_sim {
     { ProfScope pr(WL_PROF_RESIDUAL, s);
       // p's and the spare's ghost cells are +0 unless someone wrote them from outside (checked once after a pointer to p was handed out): no shell pass then
       if (comm) p_shell = 1;   // (a slab's ghost planes hold the neighbours' pressure: always scaled with the rest)
-      if (p_shell < 0) p_shell = (wl::shell_nonzero(p, G, (int*)(mg->ws.res_f + 7), s) || wl::shell_nonzero(ps, G, (int*)(mg->ws.res_f + 7), s)) ? 1 : 0;
-      WL_TRY(wl::resjac(ps, mg->lv[0].eps, p, u, G, dtl, 1.f, mg->lv[0].cl, mg->ws, 1, 0, s, p_shell != 0, df.bc_deferred ? d.uBC : nullptr, df.p_scale_pending)); }
+      if (p_shell < 0) p_shell = (wl::shell_nonzero(p, G, (int*)(mg->ws.res_f + WL_RF_IFLAG), s) || wl::shell_nonzero(ps, G, (int*)(mg->ws.res_f + WL_RF_IFLAG), s)) ? 1 : 0;
+      WL_TRY(wl::resjac(ps, mg->lv[0].eps, p, u, G, dtl, 1.f, mg->lv[0].cl, mg->ws, WL_RD_L1_INIT, WL_RF_LINF_INIT, s, p_shell != 0, df.bc_deferred ? d.uBC : nullptr, df.p_scale_pending)); }
     return use_headspec && !comm && itmx >= 1 ? head_speculate(c, dtl, plan, done, h, s) : head_read_back(h, s);
   }
   // z=div(u); x.*=dt; residual! — the scaled pressure goes to the spare array, which becomes p.  After a discarded solve p is the scaled x again, untouched: the head only read it
@@ -682,14 +681,14 @@ struct wl_sim {
            wl::conv_tile_ok(G, d.perdir_mask, G.k1 - G.k0) && mg->lv[0].cl.on;
   }
   int cfl(hipStream_t s, bool more_follow = false) {                                     // CFL :234-237
-    if (!df.cfl_done) { WL_TRY(sync_u(s)); WL_TRY(wl::cfl_dev(u, sigma, G, mg->ws, CFL_SLOT, s)); WL_TRY(wl::combine_results(comm, mg->ws, s)); }   // max over ranks
+    if (!df.cfl_done) { WL_TRY(sync_u(s)); WL_TRY(wl::cfl_dev(u, sigma, G, mg->ws, WL_RF_CFL, s)); WL_TRY(wl::combine_results(comm, mg->ws, s)); }   // max over ranks
     df.cfl_done = false;
     if (more_follow && lazydt_ok()) {
-      hipLaunchKernelGGL(k_dt_from_cfl, dim3(1), dim3(1), 0, s, mg->ws.res_f, CFL_SLOT, CFL_SLOT + 1, d.nu);
+      hipLaunchKernelGGL(k_dt_from_cfl, dim3(1), dim3(1), 0, s, mg->ws.res_f, WL_RF_CFL, WL_RF_DT, d.nu);
       df.dt_pending = true;
       return 0;
     }
-    float hf6[CFL_SLOT + 1]; WL_TRY(wl::read_results(mg->ws, nullptr, 0, hf6, CFL_SLOT + 1, s)); const float mx = hf6[CFL_SLOT];
+    float hf[WL_RF_COUNT]; WL_TRY(wl::read_results(mg->ws, nullptr, 0, hf, wl_upto(WL_RF_CFL), s)); const float mx = hf[WL_RF_CFL];
     dt.push_back(std::fmin(10.f, 1.0f / (mx + 5 * d.nu)));
     return 0;
   }
@@ -741,9 +740,9 @@ struct wl_sim {
     struct InStep { bool& f; InStep(bool& b) : f(b) { f = true; } ~InStep() { f = false; } } guard(in_step);
     if (df.dt_pending) {   // the CFL maximum of the previous step is copied back between ITS finaliser and THIS predictor, which takes Δt from the device
       if (!ev_dt) WL_HIP(hipEventCreateWithFlags(&ev_dt, hipEventDisableTiming));
-      double hd1[1]; float hf7[CFL_SLOT + 2];
-      WL_TRY(wl::read_results_overlapped(mg->ws, hd1, 1, hf7, CFL_SLOT + 2, s, ev_dt, [&]() -> int { return predict(s, mg->ws.res_f + CFL_SLOT + 1); }));
-      dt.push_back(std::fmin(10.f, 1.0f / (hf7[CFL_SLOT] + 5 * d.nu)));
+      double hd[WL_RD_COUNT]; float hf[WL_RF_COUNT];
+      WL_TRY(wl::read_results_overlapped(mg->ws, hd, wl_upto(WL_RD_SUM), hf, wl_upto(WL_RF_DT), s, ev_dt, [&]() -> int { return predict(s, mg->ws.res_f + WL_RF_DT); }));
+      dt.push_back(std::fmin(10.f, 1.0f / (hf[WL_RF_CFL] + 5 * d.nu)));
       df.dt_pending = false;
     } else
     WL_TRY(predict(s));
@@ -766,15 +765,15 @@ int wl_sim::exit_bc(hipStream_t s) {
     const long gcnt = (long)(G.ny - 2) * (G.gnz - 2), lcnt = (long)(G.ny - 2) * (G.k1 - G.k0);
     const unsigned nbl = (unsigned)((lcnt + WL_BLOCK - 1) / WL_BLOCK);
     for (int mode = 0; mode < 2; mode++) {
-      hipLaunchKernelGGL(k_exit_facesum_part<3>, dim3(1), dim3(1024), 0, s, G, (const float*)u, mg->ws.res_d + 4, mode);
+      hipLaunchKernelGGL(k_exit_facesum_part<3>, dim3(1), dim3(1024), 0, s, G, (const float*)u, mg->ws.res_d + WL_RD_EXIT, mode);
       WL_TRY(wl::combine_results(comm, mg->ws, s));
-      hipLaunchKernelGGL(k_exit_mean, dim3(1), dim3(1), 0, s, (const double*)(mg->ws.res_d + 4), exit_sc, gcnt, mode);
+      hipLaunchKernelGGL(k_exit_mean, dim3(1), dim3(1), 0, s, (const double*)(mg->ws.res_d + WL_RD_EXIT), exit_sc, gcnt, mode);
       hipLaunchKernelGGL(k_exit_update_slab<3>, dim3(nbl), dim3(WL_BLOCK), 0, s, G, u, (const float*)u0, (const double*)exit_sc, dt.back(), mode);
     }
     WL_LAUNCH_CHECK();
     return wl::halo(comm, u, G, d.D, 2, s);      // the exit face changed after BC!'s exchange
   }
-  return exit_bc_single(G, u, u0, mg->ws.res_d + 4, dt.back(), s);
+  return exit_bc_single(G, u, u0, mg->ws.res_d + WL_RD_EXIT, dt.back(), s);
 }
 
 // exitBC!(u,u⁰,Δt) on a single domain (src/core.jl:226-233): inflow mean -> convective update of the exit face (mode 0), its mean -> flux correction (mode 1)
@@ -793,7 +792,7 @@ int wl_exit_bc(float* u, const float* u0, const wl_grid* g, float dt, void* st) 
   WL_CHECK(wl_grid_ok(g), "bad wl_grid"); WL_CHECK(g->D == 2 || g->nz == g->gnz, "exitBC! needs the whole x-exit face on one rank");
   WL_TRY(wl_ctx_ensure());
   const GridX G = gx(*g); hipStream_t s = wl_stream(st);
-  return wl_sim::exit_bc_single(G, u, u0, wl_red_ws(wl_ctx().red).res_d + 4, dt, s);
+  return wl_sim::exit_bc_single(G, u, u0, wl_red_ws(wl_ctx().red).res_d + WL_RD_EXIT, dt, s);
 }
 int wl_L2_inside(const float* a, const wl_grid* g, double* out, void* st) {
   WL_CHECK(wl_grid_ok(g), "bad wl_grid"); WL_TRY(wl_ctx_ensure());
@@ -801,9 +800,9 @@ int wl_L2_inside(const float* a, const wl_grid* g, double* out, void* st) {
   const RedWs ws = wl_red_ws(wl_ctx().red);
   dim3 grid = wl_plane_grid(G, wl_red_slots(G, G.k1 - G.k0));
   DSEL(G.D, k_l2_inside, grid, dim3(WL_BLOCK), 0, s, G, a, ws.pa);
-  hipLaunchKernelGGL(k_fin1, dim3(1), dim3(WL_BLOCK), 0, s, ws.pa, (int)grid.x, ws.res_d + 0);
+  hipLaunchKernelGGL(k_fin1, dim3(1), dim3(WL_BLOCK), 0, s, ws.pa, (int)grid.x, ws.res_d + WL_RD_SUM);
   WL_LAUNCH_CHECK();
-  return wl::read_results(ws, out, 1, nullptr, 0, s);
+  return wl::read_results(ws, out, wl_upto(WL_RD_SUM), nullptr, 0, s);
 }
 
 static int sim_create_common(wl_sim** out, const wl_sim_desc* desc, wl_comm* comm, wl_mg* adopt = nullptr) {
@@ -1137,12 +1136,12 @@ int force_reduce_with(const GridX& G, const RedWs& ws, wl_comm* comm, double* ou
   dim3 grid = wl_plane_grid(G, wl_red_slots(G, G.k1 - G.k0));
   // partials need 3*grid.x doubles (<= 3*WL_REDPART): pa and pb are contiguous (2*WL_MAXPART doubles)
   WL_TRY(partials(grid, ws.pa, q));
-  hipLaunchKernelGGL(k_fin3, dim3(1), dim3(WL_BLOCK), 0, q, ws.pa, (int)grid.x, ws.res_d + 4);
+  hipLaunchKernelGGL(k_fin3, dim3(1), dim3(WL_BLOCK), 0, q, ws.pa, (int)grid.x, ws.res_d + WL_RD_FORCE);
   WL_LAUNCH_CHECK();
   WL_TRY(wl::combine_results(comm, ws, q));
   std::lock_guard<std::mutex> lock(wl::wl_read_mutex());
   WlCtx& cx = wl_ctx();
-  WL_HIP(hipMemcpyAsync(cx.h_d, ws.res_d + 4, 3 * sizeof(double), hipMemcpyDeviceToHost, q));
+  WL_HIP(hipMemcpyAsync(cx.h_d, ws.res_d + WL_RD_FORCE, 3 * sizeof(double), hipMemcpyDeviceToHost, q));
   WL_HIP(hipStreamSynchronize(q));
   for (int c = 0; c < D; c++) out[c] = cx.h_d[c];
   return 0;
@@ -1231,7 +1230,7 @@ int wl_sim_flow_stats(wl_sim* s, const float* U, double* out, void* st) {
   WL_TRY(s->settle(wl_stream(st))); WL_TRY(wl_ctx_ensure());
   const RedWs ws = wl_red_ws(wl_ctx().red);          // the library's workspace, not the solver's: the handle's state is left alone
   WL_TRY(wl::metrics_stats_dev(s->u, s->G, U, ws, wl_stream(st)));
-  float mx; WL_TRY(wl::read_results(ws, out, 2, &mx, 1, wl_stream(st)));
+  float mx; WL_TRY(wl::read_results(ws, out, wl_upto(WL_RD_SUM2), &mx, wl_upto(WL_RF_LEAF), wl_stream(st)));
   out[2] = (double)mx;
   return 0;
 }
