@@ -390,6 +390,29 @@ int wl_sim_measure_bodyset(wl_sim* s, const wl_bodyset* host_set, float eps, voi
 int wl_sim_pressure_force_bodyset(wl_sim* s, const float* host_x0, const wl_bodyset* host_set, double out[3], void* stream);   /* collective on z-slabs */
 int wl_sim_viscous_force_bodyset(wl_sim* s, const float* host_x0, const wl_bodyset* host_set, double out[3], void* stream);
 
+/* ---- force history: pressure/viscous force and moment of a body after every step, from the body's band only (src/Metrics.jl:116-195) --------
+ * nds(body,x) is zero outside |d| ≤ 1, so the sums run over a list of ACTIVE TILES — boxes of 64×4×4 array cells (2-D: 64×4) with an interior cell at
+ * d² ≤ 1, found by evaluating the body program on every interior cell, in ascending order, rebuilt only when the body changes.  One launch with one
+ * workgroup per active tile evaluates the body once per cell and accumulates all twelve Float64 sums; a single-workgroup finish adds the per-tile
+ * partials in list order.  The per-cell Float32 terms are those of the four calls above; only the (fixed) order of the Float64 additions differs.
+ * A record is 12 doubles: pressure force [0..2], viscous force [3..5], pressure moment [6..8], viscous moment [9..11] about x₀ (2-D: a vector's third
+ * slot is 0, the scalar moment sits in both of the first two).  Single-domain handles created with has_body=1; anything else returns WL_EINVAL.
+ *
+ * wl_sim_set_force_record: after every completed mom_step! of this handle (wl_sim_mom_step, each step of wl_sim_mom_steps) one record of host_set on the
+ * step's final p and u is appended on the device — two launches per step on the step's stream (one for a body with no active tile), behind the second
+ * projection and ahead of CFL, no host round trip, the step's bits untouched.  host_x0 NULL: moments about the origin.  A full buffer drops new records
+ * (wl_sim_counter "force_dropped"; "force_records": those held; "force_tiles": the list's length).  wl_sim_measure_body / _bodyset / _sphere on a handle
+ * with a recorder make the body just measured the recorder's body and rebuild the list (pressure_force(sim) means sim.body as it is now); wl_sim_update
+ * leaves it alone.  host_set NULL switches recording off.  Setting discards records not read yet.  Waits for the device. */
+int wl_sim_set_force_record(wl_sim* s, const wl_bodyset* host_set, const float* host_x0, int capacity);
+/* copies the records taken since the last read (oldest first, [n][12]) to the host; *n_records, *first_step, the query form (host_out NULL) and a too small
+ * cap_records (WL_EINVAL, nothing read) as wl_sim_read_probes.  Synchronises the stream the records were taken on; empties the buffer. */
+int wl_sim_read_forces(wl_sim* s, double* host_out, int cap_records, int* n_records, int* first_step);
+/* the same twelve numbers of host_set now, on the handle's current p and u: builds the list (kept: a repeated call with the same body launches the one
+ * pass only), runs it on the stream (a hipStream_t as void*, NULL = default) and reads back once: it synchronises that stream.  Independent of the recorder.
+ * The stream-contract scenarios of this section are tests/test_gpu_streams_forces.py. */
+int wl_sim_forces_bodyset(wl_sim* s, const float* host_x0, const wl_bodyset* host_set, double out[12], void* hip_stream);
+
 /* ---- multi-GPU: z-slab decomposition, one process per GPU (NEW — the reference has no multi-device path,
  * /root/reference/README.md:153-155).  A wl_comm carries the two primitives the slab path needs, stream-ordered:
  * a nearest-neighbour plane exchange along z and an all-gather; scalars (Σr, L₁, L∞, max σ) are combined on

@@ -47,7 +47,9 @@ int wl_placement_scores(double* out, int cap);
  * "mask_m0var_only" (only μ₀ off the wall pattern), "mask_clean_in_box" (inside the near bounding box, not near), "dirty_z0" / "dirty_z1" (first / last plane
  * with any mark; z1 < z0: none), "near_b0" / "near_b1" / "near_k0" / "near_k1" (the bounding box; b1 < b0: empty);
  * "launches" = kernel launches issued inside this handle's mom_step! calls so far (wl_launch_count is process-wide),
- * "probe_records" / "probe_dropped" = probe records held since the last wl_sim_read_probes / records a full buffer refused since wl_sim_set_probes */
+ * "probe_records" / "probe_dropped" = probe records held since the last wl_sim_read_probes / records a full buffer refused since wl_sim_set_probes;
+ * "force_records" / "force_dropped" = the same for the force recorder (wl_sim_set_force_record); "force_tiles" = active tiles of the band list in use
+ * (the recorder's, or without a recorder that of the last wl_sim_forces_bodyset) */
 int wl_sim_counter(wl_sim* s, const char* name, long* out);
 
 #ifdef __cplusplus

@@ -206,6 +206,9 @@ SIGNATURES = {
     "wl_sim_pressure_force_bodyset": (i32, [P, C.POINTER(f32), C.POINTER(wl_bodyset), C.POINTER(f64), P]),
     "wl_sim_viscous_force_bodyset": (i32, [P, C.POINTER(f32), C.POINTER(wl_bodyset), C.POINTER(f64), P]),
     "wl_sim_viscous_force_sphere": (i32, [P, C.POINTER(f32), f32, C.POINTER(f64), P]),
+    "wl_sim_set_force_record": (i32, [P, C.POINTER(wl_bodyset), C.POINTER(f32), i32]),
+    "wl_sim_read_forces": (i32, [P, C.POINTER(f64), i32, C.POINTER(i32), C.POINTER(i32)]),
+    "wl_sim_forces_bodyset": (i32, [P, C.POINTER(f32), C.POINTER(wl_bodyset), C.POINTER(f64), P]),
     "wl_interp": (i32, [P, P, G, P, sz, i32, P]),
     "wl_sim_sample": (i32, [P, P, sz, P, P, P]),
     "wl_sim_set_probes": (i32, [P, C.POINTER(f32), i32, i32]),

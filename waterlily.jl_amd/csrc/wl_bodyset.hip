@@ -9,6 +9,7 @@
 
 #include "wl_common.hpp"
 #include "wl_body.hpp"
+#include "wl_bodyset_dev.hpp"
 
 namespace {
 __device__ __forceinline__ bool cell_ij_(const GridX& g, long m, int& i, int& j) {
@@ -18,126 +19,6 @@ __device__ __forceinline__ bool cell_ij_(const GridX& g, long m, int& i, int& j)
   return true;
 }
 __device__ __forceinline__ bool interior_ij_(const GridX& g, int i, int j) { return i >= 1 && i <= g.nx - 2 && j >= 1 && j <= g.ny - 2; }
-
-// Julia's isless / isequal on Float32: NaN after everything, −0 before +0
-__device__ __forceinline__ bool jl_isless(float a, float b) {
-  if (isnan(a) || isnan(b)) return !isnan(a) && isnan(b);
-  if (a == b) return signbit(a) && !signbit(b);
-  return a < b;
-}
-__device__ __forceinline__ bool jl_isequal(float a, float b) {
-  if (isnan(a) || isnan(b)) return isnan(a) && isnan(b);
-  return a == b && signbit(a) == signbit(b);
-}
-
-// body-frame point ξ = R̂(x−x₀−xₚ)+xₚ of a mapped leaf (b = x−x₀−xₚ is kept for the velocity)   src/RigidMap.jl:37
-template <int D>
-__device__ __forceinline__ void to_body_frame(const wl_body_node& nd, const float* x, float* xi, float* b) {
-  for (int q = 0; q < D; q++) b[q] = (x[q] - nd.map.x0[q]) - nd.map.xp[q];
-  for (int q = 0; q < D; q++) { float s = 0.f; for (int r = 0; r < D; r++) s += nd.map.R[q * 3 + r] * b[r]; xi[q] = s + nd.map.xp[q]; }
-}
-// closed-form sdf of a leaf at the body-frame point ξ (src/AutoBody.jl:21)
-template <int D>
-__device__ __forceinline__ float leaf_sdf_at(const wl_body_node& b, const float* xi) {
-  if (b.kind == WL_BODY_PLANE) { float s = 0.f; for (int q = 0; q < D; q++) s += b.m[q] * (xi[q] - b.c[q]); return s; }
-  if (b.kind == WL_BODY_SPHERE) { float s = 0.f; for (int q = 0; q < D; q++) { const float dx = b.m[q] * (xi[q] - b.c[q]); s += dx * dx; } return sqrtf(s) - b.R; }
-  float t = 0.f; for (int q = 0; q < D; q++) t += b.m[q] * (xi[q] - b.c[q]);
-  t = fminf(fmaxf(t, -b.h), b.h);
-  float s = 0.f; for (int q = 0; q < D; q++) { const float dx = xi[q] - (b.c[q] + t * b.m[q]); s += dx * dx; }
-  return sqrtf(s) - b.R;
-}
-// raw sdf of a leaf at x: sdf(map(x)); an unmapped sphere/plane is body_sdf itself
-template <int D>
-__device__ __forceinline__ float leaf_sdf(const wl_body_node& b, const float* x) {
-  if (!b.mapped) return b.kind == WL_BODY_CAPSULE ? leaf_sdf_at<D>(b, x) : body_sdf<D>(body_arg(b), x);
-  float xi[3], bq[3];
-  to_body_frame<D>(b, x, xi, bq);
-  return leaf_sdf_at<D>(b, xi);
-}
-// measure(leaf,x;fastd²) -> d, n, V (n = V = 0 on the early exits)   src/AutoBody.jl:29-37
-template <int D>
-__device__ __forceinline__ void leaf_measure(const wl_body_node& b, const float* x, float fastd2, float& d, float* n, float* v) {
-  for (int q = 0; q < 3; q++) { n[q] = 0.f; v[q] = 0.f; }
-  if (!b.mapped && b.kind != WL_BODY_CAPSULE) {          // exactly wl_body's measure (V = 0)
-    BodyArg ba; ba.kind = b.kind; ba.R = b.R;
-    for (int q = 0; q < 3; q++) { ba.c[q] = b.c[q]; ba.m[q] = b.m[q]; ba.V[q] = 0.f; }
-    body_measure<D>(ba, x, fastd2, d, n);
-    return;
-  }
-  float xi[3] = {x[0], x[1], x[2]}, bq[3] = {0.f, 0.f, 0.f};
-  if (b.mapped) to_body_frame<D>(b, x, xi, bq);
-  d = leaf_sdf_at<D>(b, xi);
-  if (d * d > fastd2) return;
-  float g[3] = {0.f, 0.f, 0.f}; bool nan = false;
-  if (b.kind == WL_BODY_PLANE) { for (int q = 0; q < D; q++) g[q] = b.m[q]; }
-  else if (b.kind == WL_BODY_SPHERE) {
-    float s = 0.f; for (int q = 0; q < D; q++) { const float dx = b.m[q] * (xi[q] - b.c[q]); s += dx * dx; }
-    const float rr = sqrtf(s);
-    for (int q = 0; q < D; q++) g[q] = (b.m[q] * (xi[q] - b.c[q])) / rr;
-  } else {
-    float t = 0.f; for (int q = 0; q < D; q++) t += b.m[q] * (xi[q] - b.c[q]);
-    t = fminf(fmaxf(t, -b.h), b.h);
-    float dl[3] = {0.f, 0.f, 0.f}, s = 0.f; for (int q = 0; q < D; q++) { dl[q] = xi[q] - (b.c[q] + t * b.m[q]); s += dl[q] * dl[q]; }
-    const float rr = sqrtf(s);
-    for (int q = 0; q < D; q++) g[q] = dl[q] / rr;
-  }
-  for (int q = 0; q < D; q++) nan = nan || isnan(g[q]);
-  if (nan) return;
-  float nn[3] = {0.f, 0.f, 0.f};
-  if (b.mapped) { for (int a = 0; a < D; a++) { float s = 0.f; for (int q = 0; q < D; q++) s += b.map.R[q * 3 + a] * g[q]; nn[a] = s; } }   // J'n
-  else { for (int a = 0; a < D; a++) nn[a] = g[a]; }
-  float mm = 0.f; for (int q = 0; q < D; q++) mm += nn[q] * nn[q];
-  mm = sqrtf(mm); d /= mm;
-  for (int q = 0; q < D; q++) n[q] = nn[q] / mm;
-  if (b.mapped) {                                         // −J⁻¹∂ₜmap = V + ω×(x−x₀−xₚ)   src/RigidMap.jl:40-46
-    if (D == 2) { v[0] = b.map.V[0] + b.map.w[0] * -bq[1]; v[1] = b.map.V[1] + b.map.w[0] * bq[0]; }
-    else {
-      v[0] = b.map.V[0] + (b.map.w[1] * bq[2] - b.map.w[2] * bq[1]);
-      v[1] = b.map.V[1] + (b.map.w[2] * bq[0] - b.map.w[0] * bq[2]);
-      v[2] = b.map.V[2] + (b.map.w[0] * bq[1] - b.map.w[1] * bq[0]);
-    }
-  }
-}
-
-// measure(body::SetBody,x;fastd²): the postfix program on a per-lane stack of S tuples (d,n,V).  The stack pointer is wave-uniform
-// (it follows the program), so every access is an unrolled compare against a scalar: the stack lives in registers, never in scratch.
-template <int D, int S>
-__device__ __forceinline__ void set_measure(const SetArg& P, const float* x, float fastd2, float& d, float* n, float* v) {
-  constexpr int W = 2 * D + 1;                            // tuple width
-  float st[S][W];
-  int sp = 0;
-  for (int i = 0; i < P.n; i++) {
-    const wl_body_node& nd = P.node[i];
-    if (nd.op == WL_OP_LEAF) {
-      float dd, nq[3], vq[3];
-      leaf_measure<D>(nd, x, fastd2, dd, nq, vq);
-#pragma unroll
-      for (int s = 0; s < S; s++)
-        if (s == sp) { st[s][0] = dd; for (int q = 0; q < D; q++) { st[s][1 + q] = nq[q]; st[s][1 + D + q] = vq[q]; } }
-      sp++;
-    } else if (nd.op == WL_OP_NEGATE) {
-#pragma unroll
-      for (int s = 0; s < S; s++)
-        if (s == sp - 1) for (int q = 0; q <= D; q++) st[s][q] = -st[s][q];
-    } else {                                              // min / max on tuples: isless(b,a) ? b : a  /  isless(b,a) ? a : b
-#pragma unroll
-      for (int s = 1; s < S; s++)
-        if (s == sp - 1) {
-          bool less = false, eq = true;
-          for (int q = 0; q < W; q++)
-            if (eq) { less = jl_isless(st[s][q], st[s - 1][q]); eq = !less && jl_isequal(st[s][q], st[s - 1][q]); }
-          const bool takeb = (nd.op == WL_OP_UNION) ? less : !less;
-          if (takeb) for (int q = 0; q < W; q++) st[s - 1][q] = st[s][q];
-        }
-      sp--;
-    }
-  }
-  d = st[0][0];
-  for (int q = 0; q < 3; q++) { n[q] = q < D ? st[0][1 + q] : 0.f; v[q] = q < D ? st[0][1 + D + q] : 0.f; }
-}
-// kernels are templated on DS = 16·D + S (dimension, stack slots) so that one DSEL-style macro picks the instantiation
-#define DS_D (DS / 16)
-#define DS_S (DS % 16)
 
 // measure!(flow,body;ϵ)   src/Body.jl:28-51 without the two BC! calls: every element of μ₀, μ₁, V and the interior of σ in one pass
 // (the fill of :29 folded in).  Grid: every plane of the array.
@@ -192,14 +73,8 @@ __global__ void __launch_bounds__(WL_BLOCK) k_pforce_set(GridX g, const float* _
       float d, n[3], v[3]; set_measure<D, S>(P, x, 1.f, d, n, v);
       const float kk = kern_(fminf(fmaxf(d, -1.f), 1.f));
       const float pv = p[m + (long)k * g.sz];
-      if (mo.on) {
-        float nds[3] = {0.f, 0.f, 0.f}, rr[3] = {0.f, 0.f, 0.f}, cr[3];
-        for (int a = 0; a < D; a++) { nds[a] = n[a] * kk; rr[a] = x[a] - mo.x0[a]; }
-        cross_<D>(rr, nds, cr);
-        for (int a = 0; a < D; a++) acc[a] += (double)(pv * cr[a]);
-      } else {
-        for (int a = 0; a < D; a++) acc[a] += (double)(pv * (n[a] * kk));
-      }
+      float t[3]; pforce_cell<D>(mo.on, mo.x0, pv, n, kk, x, t);
+      for (int a = 0; a < D; a++) acc[a] += (double)t[a];
     }
   }
   const long b = blockIdx.x, nb = gridDim.x;
@@ -221,27 +96,8 @@ __global__ void __launch_bounds__(WL_BLOCK) k_vforce_set(GridX g, const float* _
       float d, n[3], v[3]; set_measure<D, S>(P, x, 1.f, d, n, v);
       const float kk = kern_(fminf(fmaxf(d, -1.f), 1.f));
       const long o = m + (long)k * g.sz;
-      auto du = [&](int a, int b) -> float {
-        const float* __restrict__ f = u + (long)a * g.cs;
-        if (a == b) return f[o + st[a]] - f[o];
-        return (f[o + st[b]] + f[o + st[b] + st[a]] - f[o - st[b]] - f[o - st[b] + st[a]]) / 4;
-      };
-      if (mo.on) {
-        float sn[3] = {0.f, 0.f, 0.f}, rr[3] = {0.f, 0.f, 0.f}, cr[3];
-        for (int a = 0; a < D; a++) {
-          float vs = 0.f;
-          for (int b = 0; b < D; b++) { const float Sab = (du(a, b) + du(b, a)) / 2; vs += Sab * (n[b] * kk); }
-          sn[a] = vs; rr[a] = x[a] - mo.x0[a];
-        }
-        cross_<D>(rr, sn, cr);
-        for (int a = 0; a < D; a++) acc[a] += (double)((-2 * nu) * cr[a]);
-      } else {
-        for (int a = 0; a < D; a++) {
-          float vs = 0.f;
-          for (int b = 0; b < D; b++) { const float Sab = (du(a, b) + du(b, a)) / 2; vs += ((-2 * nu) * Sab) * (n[b] * kk); }
-          acc[a] += (double)vs;
-        }
-      }
+      float t[3]; vforce_cell<D>(mo.on, mo.x0, u, g.cs, o, st, nu, n, kk, x, t);
+      for (int a = 0; a < D; a++) acc[a] += (double)t[a];
     }
   }
   const long b = blockIdx.x, nb = gridDim.x;
@@ -260,12 +116,6 @@ __global__ void __launch_bounds__(WL_BLOCK) k_points_set(SetArg P, const float* 
 }
 }  // namespace
 
-// instantiations: stack of 2 (every left-deep chain a∘b∘c∘…, a single leaf) or WL_BODYSET_STACK slots
-#define BSEL(D, S, KERN, ...)                                                                                                        \
-  do {                                                                                                                                \
-    if ((D) == 3) { if ((S) <= 2) hipLaunchKernelGGL(KERN<50>, __VA_ARGS__); else hipLaunchKernelGGL(KERN<48 + WL_BODYSET_STACK>, __VA_ARGS__); } \
-    else { if ((S) <= 2) hipLaunchKernelGGL(KERN<34>, __VA_ARGS__); else hipLaunchKernelGGL(KERN<32 + WL_BODYSET_STACK>, __VA_ARGS__); }           \
-  } while (0)
 
 namespace wl {
 int bodyset_prepare(int D, const wl_bodyset* s, SetArg* out) {

@@ -11,6 +11,7 @@
 #include "wl_mg.hpp"
 #include "wl_body.hpp"
 #include "wl_pdefer.hpp"
+#include "wl_forces.hpp"
 
 namespace {
 __device__ __forceinline__ bool cell_ij(const GridX& g, long m, int& i, int& j) {
@@ -288,7 +289,7 @@ struct wl_sim {
   // makes memory current for a reader outside the step (fields handed out, force read-outs, wl_sim_phase, a failed step).  Between calls nothing is pending but, on
   // slabs, the exchange — "a call never returns with the divisor pending", every projection ends with BC! applied — so this launches nothing there.
   int settle(hipStream_t s) { WL_TRY(sync_u(s)); WL_TRY(materialise_p(s)); return flush_bc(s); }
-  ~wl_sim() { if (df.u_pending && comm && comm->cs) (void)hipStreamSynchronize(comm->cs); if (own_mg) delete mg; if (own) (void)hipFree(own); if (exit_sc) (void)hipFree(exit_sc); if (farmask) (void)hipFree(farmask); if (mnear) (void)hipFree(mnear); if (mneedf) (void)hipFree(mneedf); if (mm0var) (void)hipFree(mm0var); free_probes(); free_tracers(); }
+  ~wl_sim() { if (df.u_pending && comm && comm->cs) (void)hipStreamSynchronize(comm->cs); if (own_mg) delete mg; if (own) (void)hipFree(own); if (exit_sc) (void)hipFree(exit_sc); if (farmask) (void)hipFree(farmask); if (mnear) (void)hipFree(mnear); if (mneedf) (void)hipFree(mneedf); if (mm0var) (void)hipFree(mm0var); free_probes(); free_tracers(); free_forces(); fimm.release(); }
 
   // BC!(u) on the physical faces this rank holds, then the z-halo planes (depth 2: QUICK reads f[I-2δ], src/Flow.jl:8)
   // On slabs the exchange runs on the communicator's own stream; the compute stream waits for it (sync_u) only where the halo
@@ -541,7 +542,7 @@ struct wl_sim {
   }
   bool skip_p_now(const ProjCall& c) const {      // decided per launch: a back-off during the head withdraws it
     if (!pdefer_ok()) return false;
-    if (c.with_cfl) return c.step_follows && !probe_m;              // the corrector's tail: the next reader is the next step's head — unless the probe record of this step reads p first
+    if (c.with_cfl) return c.step_follows && !probe_m && !force_on;   // the corrector's tail: the next reader is the next step's head — unless the probe or force record of this step reads p first
     return c.corrector_follows && (!p_home || c.step_follows || p == p_home);   // the predictor's tail: the corrector's head (caller-owned p, last step of the call: see the parity rule above)
   }
   // go != nullptr: queued inside the solver loop ahead of its read — runs iff the flag says "converged"; a gated tail that was withheld is launched again with go = nullptr.
@@ -702,6 +703,19 @@ struct wl_sim {
   hipStream_t obs_stream = nullptr;                    // the stream the last record went to (wl_sim_read_probes waits for it)
   long n_step_launches = 0;                            // kernel launches of this handle's mom_step! calls (wl_sim_counter "launches")
   void free_probes() { if (probe_x) (void)hipFree(probe_x); if (probe_rec) (void)hipFree(probe_rec); probe_x = probe_rec = nullptr; probe_m = probe_cap = probe_n = 0; }
+  // the force recorder (wl_sim_set_force_record; kernels in wl_forces.hip): after every completed step 12 doubles — pressure force, viscous force, pressure and
+  // viscous moment about force_x0 — of the recorder's body on the step's final p and u, from the body's band only.  Two launches per step (one for an empty
+  // band), no host round trip.  fimm: the band of the immediate read-out wl_sim_forces_bodyset, kept so that a repeated call finds its list built.
+  wl::ForceBand fband, fimm;
+  bool force_on = false;
+  float force_x0[3] = {0.f, 0.f, 0.f};
+  double* force_rec = nullptr;                         // device: capacity records of 12 doubles
+  int force_cap = 0, force_n = 0;
+  long force_first = 0, n_force_dropped = 0;
+  hipStream_t force_stream = nullptr;                  // the stream the last record went to (wl_sim_read_forces waits for it)
+  void free_forces() { if (force_rec) (void)hipFree(force_rec); force_rec = nullptr; force_cap = force_n = 0; force_on = false; fband.release(); }
+  // measure!(sim) replaced the body: pressure_force(sim) always means sim.body as it is now, so the recorder follows it
+  int force_body_changed(const SetArg& P, hipStream_t s) { return force_on ? fband.build(G, P, s) : 0; }
   void free_tracers() { if (tr_x) (void)hipFree(tr_x); if (tr_x0) (void)hipFree(tr_x0); tr_x = tr_x0 = nullptr; tr_n = 0; }
   int observe(hipStream_t s) {      // dt.back() is still the Δt this step ran with: cfl appends the next one afterwards
     if (probe_m) {
@@ -712,6 +726,15 @@ struct wl_sim {
         WL_TRY(wl::interp_points(u, p, G, probe_x, (size_t)probe_m, rec, d.D + 1, rec + d.D, d.D + 1, s));
         if (probe_n++ == 0) probe_first = (long)dt.size() - 1;
         obs_stream = s;
+      }
+    }
+    if (force_on) {
+      WL_TRY(materialise_p(s));     // (guard, as above)
+      if (force_n == force_cap) n_force_dropped++;
+      else {
+        WL_TRY(fband.run(G, p, u, d.nu, force_x0, force_rec + (size_t)force_n * 12, s));
+        if (force_n++ == 0) force_first = (long)dt.size() - 1;
+        force_stream = s;
       }
     }
     if (tr_n) WL_TRY(wl::advect(tr_x, tr_x0, u0, u, G, tr_n, dt.back(), d.perdir_mask, s));
@@ -1046,6 +1069,9 @@ int wl_sim_counter(wl_sim* s, const char* name, long* out) {
   if (n == "launches") { *out = s->n_step_launches; return 0; }                    // kernel launches of this handle's mom_step! calls so far
   if (n == "probe_records") { *out = s->probe_n; return 0; }                       // probe records held / refused by a full buffer
   if (n == "probe_dropped") { *out = s->n_probe_dropped; return 0; }
+  if (n == "force_records") { *out = s->force_n; return 0; }                       // force records held / refused by a full buffer / active tiles of the list in use
+  if (n == "force_dropped") { *out = s->n_force_dropped; return 0; }
+  if (n == "force_tiles") { *out = s->force_on ? s->fband.n_active : s->fimm.n_active; return 0; }
   wl_set_error("unknown counter " + n); return WL_EINVAL;
 }
 int wl_sim_set_forcing(wl_sim* s, const float* U1, const float* a0, const float* a1) {
@@ -1197,6 +1223,13 @@ int wl_sim_measure_body(wl_sim* s, const wl_body* body, float eps, void* st) {
   WL_TRY(measure_fields(s->sigma, s->mu0, s->mu1, s->V, G, bd, eps, s->d.exitBC, s->d.perdir_mask, q));
   WL_TRY(wl::halo(s->comm, s->mu0, G, D, 2, q)); WL_TRY(wl::halo(s->comm, s->V, G, D, 2, q));
   WL_TRY(s->refresh_body_mask(q));
+  if (s->force_on) {      // the recorder's body is the one just measured: the one-leaf program of this wl_body
+    wl_bodyset one{}; one.n = 1; wl_body_node& nd = one.node[0];
+    nd.op = WL_OP_LEAF; nd.kind = body->kind; nd.R = body->R;
+    for (int c = 0; c < 3; c++) { nd.c[c] = body->c[c]; nd.m[c] = body->m[c]; }
+    SetArg P; WL_TRY(wl::bodyset_prepare(D, &one, &P));
+    WL_TRY(s->force_body_changed(P, q));
+  }
   return s->mg->update(q);                                                                                                          // WaterLily.jl:148
 }
 int wl_sim_pressure_force_body(wl_sim* s, const wl_body* body, double* out, void* st) { return sim_force_body(0, s, nullptr, body, out, st); }
@@ -1208,6 +1241,7 @@ int wl_sim_measure_bodyset(wl_sim* s, const wl_bodyset* set, float eps, void* st
   WL_TRY(wl::bodyset_measure_fields(s->sigma, s->mu0, s->mu1, s->V, G, P, eps, s->d.exitBC, s->d.perdir_mask, q));
   WL_TRY(wl::halo(s->comm, s->mu0, G, D, 2, q)); WL_TRY(wl::halo(s->comm, s->V, G, D, 2, q));
   WL_TRY(s->refresh_body_mask(q));
+  WL_TRY(s->force_body_changed(P, q));
   return s->mg->update(q);                                                                                                          // WaterLily.jl:148
 }
 static int sim_force_bodyset(int which, wl_sim* s, const float* x0, const wl_bodyset* set, double* out, void* st) {
@@ -1278,6 +1312,50 @@ int wl_sim_read_probes(wl_sim* s, float* host_out, int cap_records, int* n_recor
     WL_HIP(hipStreamSynchronize(s->obs_stream));
   }
   s->probe_n = 0;
+  return 0;
+}
+static int force_handle_ok(wl_sim* s, const char* who) {
+  WL_CHECK(s, "null wl_sim");
+  if (s->comm) { wl_set_error(std::string(who) + ": z-slab handles are not supported (single domain only)"); return WL_EINVAL; }
+  if (!s->d.has_body) { wl_set_error(std::string(who) + ": the simulation was created with has_body=0"); return WL_EINVAL; }
+  return 0;
+}
+int wl_sim_set_force_record(wl_sim* s, const wl_bodyset* host_set, const float* host_x0, int capacity) {
+  WL_TRY(force_handle_ok(s, "wl_sim_set_force_record"));
+  SetArg P;
+  if (host_set) { WL_CHECK(capacity >= 1, "wl_sim_set_force_record: capacity < 1"); WL_TRY(wl::bodyset_prepare(s->d.D, host_set, &P)); }
+  WL_HIP(hipDeviceSynchronize());      // records may still be in flight on the stream of the last step
+  s->free_forces(); s->n_force_dropped = 0;
+  if (!host_set) return 0;
+  WL_HIP(hipMalloc((void**)&s->force_rec, (size_t)capacity * 12 * sizeof(double)));
+  for (int c = 0; c < 3; c++) s->force_x0[c] = (host_x0 && c < s->d.D) ? host_x0[c] : 0.f;
+  const int rc = s->fband.build(s->G, P, 0);
+  if (rc != 0) { s->free_forces(); return rc; }
+  s->force_cap = capacity; s->force_on = true;
+  return 0;
+}
+int wl_sim_read_forces(wl_sim* s, double* host_out, int cap_records, int* n_records, int* first_step) {
+  WL_CHECK(s && n_records && first_step, "wl_sim_read_forces: null handle or result");
+  *n_records = s->force_n; *first_step = (int)s->force_first;
+  if (!host_out) return 0;             // a query: nothing is copied, the buffer keeps its records
+  WL_CHECK(cap_records >= s->force_n, "wl_sim_read_forces: host_out takes fewer records than the buffer holds (nothing was read)");
+  if (s->force_n) {
+    WL_HIP(hipMemcpyAsync(host_out, s->force_rec, (size_t)s->force_n * 12 * sizeof(double), hipMemcpyDeviceToHost, s->force_stream));
+    WL_HIP(hipStreamSynchronize(s->force_stream));
+  }
+  s->force_n = 0;
+  return 0;
+}
+int wl_sim_forces_bodyset(wl_sim* s, const float* host_x0, const wl_bodyset* host_set, double out[12], void* st) {
+  WL_TRY(force_handle_ok(s, "wl_sim_forces_bodyset"));
+  WL_CHECK(out, "wl_sim_forces_bodyset: null result");
+  SetArg P; WL_TRY(wl::bodyset_prepare(s->d.D, host_set, &P));
+  hipStream_t q = wl_stream(st);
+  WL_TRY(s->settle(q));
+  WL_TRY(s->fimm.build(s->G, P, q));      // (a repeated call with the same body finds the list built: no launch, no read-back)
+  WL_TRY(s->fimm.run(s->G, s->p, s->u, s->d.nu, host_x0, s->fimm.out, q));
+  WL_HIP(hipMemcpyAsync(out, s->fimm.out, 12 * sizeof(double), hipMemcpyDeviceToHost, q));
+  WL_HIP(hipStreamSynchronize(q));
   return 0;
 }
 int wl_sim_set_tracers(wl_sim* s, const float* host_x, size_t n) {

@@ -609,5 +609,29 @@ function WaterLily.viscous_moment(x₀, u::HA, ν, df, body::DeviceSet, t=0)
     out[1:D]
 end
 
+# next to set_probes!/read_probes above (placed here: the signatures need DeviceSet) — force records inside mom_step! (pressure_force, viscous_force, pressure_moment, viscous_moment of `body` about x₀ after every step, from the body's band
+# only): room for `capacity` steps; read_forces returns (first step's index into flow.Δt (1-based), records 12×k: pF, vF, pM, vM, three slots each)
+function set_force_record!(b::HipMultiLevel, body::DeviceSet, D::Integer, capacity::Integer; x₀=nothing, t=zero(Float32))
+    @assert b.sim != C_NULL "set_force_record!: take a step first (the composite handle is created by the first mom_step!)"
+    device_ok(body) || error("set_force_record!: the body has leaves the device cannot evaluate")
+    x = x₀ === nothing ? Ptr{Cfloat}(C_NULL) : collect(pad3(x₀))
+    chk(ccall((:wl_sim_set_force_record, libwlhip), Cint, (Ptr{Cvoid}, Ref{WlBodySet}, Ptr{Cfloat}, Cint), b.sim, wlset(body, D, t), x, Cint(capacity)))
+end
+clear_force_record!(b::HipMultiLevel) = chk(ccall((:wl_sim_set_force_record, libwlhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cfloat}, Cint), b.sim, C_NULL, Ptr{Cfloat}(C_NULL), Cint(0)))
+function read_forces(b::HipMultiLevel)
+    k = Ref{Cint}(0); first = Ref{Cint}(0)
+    chk(ccall((:wl_sim_read_forces, libwlhip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ref{Cint}, Ref{Cint}), b.sim, Ptr{Cdouble}(C_NULL), Cint(0), k, first))
+    rec = Array{Float64,2}(undef, 12, Int(k[]))
+    chk(ccall((:wl_sim_read_forces, libwlhip), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ref{Cint}, Ref{Cint}), b.sim, rec, k[], k, first))
+    Int(first[]) + 1, rec
+end
+# the same twelve numbers now, on the composite's current p and u: one pass over the band, one read-back
+function forces(b::HipMultiLevel, body::DeviceSet, D::Integer; x₀=nothing, t=zero(Float32))
+    @assert b.sim != C_NULL "forces: take a step first (the composite handle is created by the first mom_step!)"
+    out = zeros(Cdouble, 12); x = x₀ === nothing ? Ptr{Cfloat}(C_NULL) : collect(pad3(x₀))
+    chk(ccall((:wl_sim_forces_bodyset, libwlhip), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Ref{WlBodySet}, Ptr{Cdouble}, Ptr{Cvoid}), b.sim, x, wlset(body, D, t), out, C_NULL))
+    out
+end
+
 export HipArray, HipMultiLevel, HipBody, HipCapsule, HipRigidBody
 end # module

@@ -20,6 +20,31 @@ def _x0(x0, D):
     return None if x0 is None else (C.c_float * 3)(*([float(v) for v in x0] + [0.0] * (3 - D)))
 
 
+def _as_set(body):
+    """a composite body as it is; a closed-form tuple — ("sphere", c, R), ("cylinder", c, R, axis), ("plane", point, normal), ("capsule", …) — as its leaf"""
+    from .bodies import Body
+    if _is_set(body):
+        return body
+    if isinstance(body, (tuple, list)) and body and isinstance(body[0], str):
+        return Body(tuple(body))
+    raise TypeError(f"a body of bodies.py or a closed-form tuple is expected, not {type(body).__name__}")
+
+
+def _x0_checked(x0, D):
+    if x0 is None:
+        return None
+    x0 = [float(v) for v in x0]
+    if len(x0) != D:
+        raise ValueError(f"x0 has {len(x0)} components, the flow has {D}")
+    return _x0(x0, D)
+
+
+def _split_forces(rec, D):
+    """[k,12] records -> pF[k,D], vF[k,D], pM[k,·], vM[k,·] (the moment is a scalar in 2-D: one column)"""
+    M = 3 if D == 3 else 1
+    return rec[:, 0:D].copy(), rec[:, 3:3 + D].copy(), rec[:, 6:6 + M].copy(), rec[:, 9:9 + M].copy()
+
+
 def _bodyset_force(which, a, body, x0=None):
     """pressure (which 0) / viscous (1) force, or the moment about x0, of a composite body (bodies.py) on a Flow"""
     from .core import sgrid
@@ -342,7 +367,7 @@ class FusedSimulation:
         check(lib().wl_sim_set_option(self._h, name.encode(), int(value)))
 
     def counter(self, name):
-        """path counters of the handle (include/wlhip_bench.h wl_sim_counter): "resjac", "resjac_redo", "resjac_backoff", "xdefer", "tailfuse", "bcdefer", "pdefer", "tailwide", "rskip", "rskip_redo", "tailspec", "tailspec_armed", "launches", "probe_records", "probe_dropped"; "tailfuse_min" reads the size gate of "tailfuse" in force;
+        """path counters of the handle (include/wlhip_bench.h wl_sim_counter): "resjac", "resjac_redo", "resjac_backoff", "xdefer", "tailfuse", "bcdefer", "pdefer", "tailwide", "rskip", "rskip_redo", "tailspec", "tailspec_armed", "launches", "probe_records", "probe_dropped", "force_records", "force_dropped", "force_tiles"; "tailfuse_min" reads the size gate of "tailfuse" in force;
         with a body: "hybrid", "body_tile", "mask_valid", "part", "part_za", "part_zb" and the mask census "mask_near", "mask_needf_only", "mask_m0var_only",
         "mask_clean_in_box", "dirty_z0", "dirty_z1", "near_b0", "near_b1", "near_k0", "near_k1" """
         v = C.c_long(0)
@@ -547,6 +572,38 @@ class FusedSimulation:
         ends = np.cumsum(np.asarray(self.dt, dtype=np.float32), dtype=np.float32)      # ends[j] = sum(Δt[1:j+1]), summed in order in Float32
         t = ends[first.value:first.value + k.value].astype(np.float64)
         return t, rec[:, :, :D].copy(), rec[:, :, D].copy()
+
+    def set_force_record(self, body, x0=None, capacity=1024):
+        """record pressure force, viscous force and both moments about x0 (None: the origin) of `body` after every completed step of this handle —
+        mom_step_ and each step inside mom_steps_ — for up to `capacity` steps between two read_forces(); evaluated on the device from the body's band
+        only (two launches per step, no host round trip).  body: a body of bodies.py or a closed-form tuple; None switches recording off.  A later
+        measure!(sim) of this handle (set_body, measure_body_, measure_sphere_, sim_step_(remeasure=True)) makes the body it measures the recorded one."""
+        if body is None:
+            check(lib().wl_sim_set_force_record(self._h, None, None, 0))
+            return
+        if int(capacity) < 1:
+            raise ValueError("capacity must be at least 1")
+        prog = _as_set(body).program(self.D)
+        check(lib().wl_sim_set_force_record(self._h, C.byref(prog), _x0_checked(x0, self.D), int(capacity)))
+
+    def read_forces(self):
+        """(t, pF[k,D], vF[k,D], pM[k,·], vM[k,·]) of the k records taken since the last read, oldest first (Float64; the moments have three columns in
+        3-D, one in 2-D); t as in read_probes.  Empties the buffer."""
+        k, first = C.c_int(0), C.c_int(0)
+        check(lib().wl_sim_read_forces(self._h, None, 0, C.byref(k), C.byref(first)))
+        rec = np.empty((k.value, 12), dtype=np.float64)
+        check(lib().wl_sim_read_forces(self._h, rec.ctypes.data_as(C.POINTER(C.c_double)), k.value, C.byref(k), C.byref(first)))
+        ends = np.cumsum(np.asarray(self.dt, dtype=np.float32), dtype=np.float32)
+        t = ends[first.value:first.value + k.value].astype(np.float64)
+        return (t,) + _split_forces(rec, self.D)
+
+    def forces(self, body, x0=None):
+        """(pF[D], vF[D], pM[·], vM[·]) of `body` on the current p and u in one pass over the body's band and one read-back: what pressure_force_body,
+        viscous_force_body, pressure_moment_body and viscous_moment_body return, summed from the same per-cell terms"""
+        prog = _as_set(body).program(self.D)
+        out = (C.c_double * 12)()
+        check(lib().wl_sim_forces_bodyset(self._h, _x0_checked(x0, self.D), C.byref(prog), out, stream()))
+        return tuple(a[0] for a in _split_forces(np.array(out[:], dtype=np.float64)[None, :], self.D))
 
     def set_tracers(self, points):
         """a swarm of tracer particles at the (n, D) host points, advanced by every completed step of this handle (wl_advect with u⁰, the final u and
