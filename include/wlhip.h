@@ -413,6 +413,30 @@ int wl_sim_read_forces(wl_sim* s, double* host_out, int cap_records, int* n_reco
  * The stream-contract scenarios of this section are tests/test_gpu_streams_forces.py. */
 int wl_sim_forces_bodyset(wl_sim* s, const float* host_x0, const wl_bodyset* host_set, double out[12], void* hip_stream);
 
+/* ---- mean flow: MeanFlow's time averages P, U and UU = ⟨u⊗u⟩ as an observer of a handle (src/Metrics.jl:205-262) --------
+ * The handle owns P (cs floats, cs = cells of one scalar array, ghost cells included), U (D·cs) and — mode 2 — UU, zero-initialised, and the time vector t.
+ * UU is stored PACKED: the components i ≤ j only, plane i + j(j+1)/2 of cs floats (3 planes in 2-D, 6 in 3-D); UU[I,i,j] and UU[I,j,i] are the same bits.
+ * After every `every`-th completed mom_step! since set/reset (wl_sim_mom_step, each step of wl_sim_mom_steps) ONE launch on the step's stream, behind the second
+ * projection and ahead of CFL, applies update! (:236-248) to every cell on the step's final p and u: ε = dt/(dt + (t[end]−t[1]) + eps(Float32)) in Float32 on
+ * the host with dt = time(flow) − t[end], ε = 1 on the first update; time(flow) is sum(Δt) with the step's own Δt included, what wl_sim_time returns after the
+ * step.  On a step that ends with an update the corrector's projection tail stores p where option "pdefer" would skip it (same bits on every cell); other steps
+ * launch nothing and defer as without the observer.  Nothing the step reads is written.  Single-domain handles; a z-slab handle returns WL_EINVAL.
+ * Counters: wl_sim_counter "mean_updates" (since set), "mean_every" (0: off).  The stream-contract scenarios are tests/test_gpu_streams_meanflow.py.
+ *
+ * wl_sim_set_meanflow: mode 0 off (frees the averages), 1 P and U, 2 P, U and UU; t_init NaN: time(flow).  The zero fill goes to `hip_stream`; a change of
+ * mode waits for the stream of the last update first.  A failed allocation frees everything and returns the error. */
+int wl_sim_set_meanflow(wl_sim* s, int mode, int every, float t_init, void* hip_stream);
+/* reset!(meanflow; t_init) :229-234: zeroes the averages (on the stream), t = [t_init] (NaN: time(flow)); the period counts from here */
+int wl_sim_meanflow_reset(wl_sim* s, float t_init, void* hip_stream);
+/* update!(meanflow, flow) now, on the handle's current u and p with time(flow) = wl_sim_time; independent of `every`; one launch, asynchronous */
+int wl_sim_meanflow_update(wl_sim* s, void* hip_stream);
+/* device pointer to P (which 0), U (1) or the packed UU (2; NULL unless mode 2) and its length in floats; valid until the next wl_sim_set_meanflow */
+float* wl_sim_meanflow(wl_sim* s, int which, size_t* n);
+/* the packed UU expanded into the caller's device array out[cs·D·D] in the reference's (N…, D, D) layout; tau != 0: uu!'s τ[I,i,j] = UU[I,i,j] − U[I,i]·U[I,j] (:250-252) */
+int wl_sim_meanflow_uu(wl_sim* s, float* out, int tau, void* hip_stream);
+/* meanflow.t: copies min(length, cap) entries to host `out` (NULL: none) and returns the length */
+int wl_sim_meanflow_t(const wl_sim* s, float* out, int cap);
+
 /* ---- multi-GPU: z-slab decomposition, one process per GPU (NEW — the reference has no multi-device path,
  * /root/reference/README.md:153-155).  A wl_comm carries the two primitives the slab path needs, stream-ordered:
  * a nearest-neighbour plane exchange along z and an all-gather; scalars (Σr, L₁, L∞, max σ) are combined on

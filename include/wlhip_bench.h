@@ -49,7 +49,8 @@ int wl_placement_scores(double* out, int cap);
  * "launches" = kernel launches issued inside this handle's mom_step! calls so far (wl_launch_count is process-wide),
  * "probe_records" / "probe_dropped" = probe records held since the last wl_sim_read_probes / records a full buffer refused since wl_sim_set_probes;
  * "force_records" / "force_dropped" = the same for the force recorder (wl_sim_set_force_record); "force_tiles" = active tiles of the band list in use
- * (the recorder's, or without a recorder that of the last wl_sim_forces_bodyset) */
+ * (the recorder's, or without a recorder that of the last wl_sim_forces_bodyset);
+ * "mean_updates" = updates of the mean-flow observer since wl_sim_set_meanflow (the observer's and wl_sim_meanflow_update's), "mean_every" = its period (0: off) */
 int wl_sim_counter(wl_sim* s, const char* name, long* out);
 
 #ifdef __cplusplus

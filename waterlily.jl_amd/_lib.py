@@ -216,6 +216,12 @@ SIGNATURES = {
     "wl_advect": (i32, [P, P, P, P, G, sz, f32, u32, P]),
     "wl_sim_set_tracers": (i32, [P, C.POINTER(f32), sz]),
     "wl_sim_tracers": (P, [P, i32, C.POINTER(sz)]),
+    "wl_sim_set_meanflow": (i32, [P, i32, i32, f32, P]),
+    "wl_sim_meanflow_reset": (i32, [P, f32, P]),
+    "wl_sim_meanflow_update": (i32, [P, P]),
+    "wl_sim_meanflow": (P, [P, i32, C.POINTER(sz)]),
+    "wl_sim_meanflow_uu": (i32, [P, P, i32, P]),
+    "wl_sim_meanflow_t": (i32, [P, C.POINTER(f32), i32]),
 }
 
 _lib = None

@@ -12,6 +12,7 @@
 #include "wl_body.hpp"
 #include "wl_pdefer.hpp"
 #include "wl_forces.hpp"
+#include "wl_meanflow.hpp"
 
 namespace {
 __device__ __forceinline__ bool cell_ij(const GridX& g, long m, int& i, int& j) {
@@ -289,7 +290,7 @@ struct wl_sim {
   // makes memory current for a reader outside the step (fields handed out, force read-outs, wl_sim_phase, a failed step).  Between calls nothing is pending but, on
   // slabs, the exchange — "a call never returns with the divisor pending", every projection ends with BC! applied — so this launches nothing there.
   int settle(hipStream_t s) { WL_TRY(sync_u(s)); WL_TRY(materialise_p(s)); return flush_bc(s); }
-  ~wl_sim() { if (df.u_pending && comm && comm->cs) (void)hipStreamSynchronize(comm->cs); if (own_mg) delete mg; if (own) (void)hipFree(own); if (exit_sc) (void)hipFree(exit_sc); if (farmask) (void)hipFree(farmask); if (mnear) (void)hipFree(mnear); if (mneedf) (void)hipFree(mneedf); if (mm0var) (void)hipFree(mm0var); free_probes(); free_tracers(); free_forces(); fimm.release(); }
+  ~wl_sim() { if (df.u_pending && comm && comm->cs) (void)hipStreamSynchronize(comm->cs); if (own_mg) delete mg; if (own) (void)hipFree(own); if (exit_sc) (void)hipFree(exit_sc); if (farmask) (void)hipFree(farmask); if (mnear) (void)hipFree(mnear); if (mneedf) (void)hipFree(mneedf); if (mm0var) (void)hipFree(mm0var); free_probes(); free_tracers(); free_forces(); free_mean(); fimm.release(); }
 
   // BC!(u) on the physical faces this rank holds, then the z-halo planes (depth 2: QUICK reads f[I-2δ], src/Flow.jl:8)
   // On slabs the exchange runs on the communicator's own stream; the compute stream waits for it (sync_u) only where the halo
@@ -542,7 +543,7 @@ struct wl_sim {
   }
   bool skip_p_now(const ProjCall& c) const {      // decided per launch: a back-off during the head withdraws it
     if (!pdefer_ok()) return false;
-    if (c.with_cfl) return c.step_follows && !probe_m && !force_on;   // the corrector's tail: the next reader is the next step's head — unless the probe or force record of this step reads p first
+    if (c.with_cfl) return c.step_follows && !probe_m && !force_on && !mean_due();   // the corrector's tail: the next reader is the next step's head — unless the probe or force record or the mean-flow update of this step reads p first
     return c.corrector_follows && (!p_home || c.step_follows || p == p_home);   // the predictor's tail: the corrector's head (caller-owned p, last step of the call: see the parity rule above)
   }
   // go != nullptr: queued inside the solver loop ahead of its read — runs iff the flag says "converged"; a gated tail that was withheld is launched again with go = nullptr.
@@ -716,6 +717,36 @@ struct wl_sim {
   void free_forces() { if (force_rec) (void)hipFree(force_rec); force_rec = nullptr; force_cap = force_n = 0; force_on = false; fband.release(); }
   // measure!(sim) replaced the body: pressure_force(sim) always means sim.body as it is now, so the recorder follows it
   int force_body_changed(const SetArg& P, hipStream_t s) { return force_on ? fband.build(G, P, s) : 0; }
+  // the mean-flow observer (wl_sim_set_meanflow; kernels in wl_meanflow.hip): MeanFlow's P, U and — mode 2 — UU = ⟨u⊗u⟩ (src/Metrics.jl:205-262), updated by ONE
+  // launch after every mean_every-th completed step on the step's final p and u, every cell of the arrays.  ε and the time vector are update!'s Float32
+  // statements on the host (:237-239,247); time(flow) is the in-order sum of the Δt history, this step's Δt included — what wl_sim_time returns once cfl has
+  // appended the next one.  UU is packed (i ≤ j: wl_meanflow.hip).  Steps on which no update is due launch nothing and defer as a handle without the observer.
+  float* mean_own = nullptr;                           // device: P (cs) | U (D·cs) | packed UU (D(D+1)/2·cs, mode 2), zero-initialised
+  int mean_mode = 0, mean_every = 1;                   // 0 off, 1 P and U, 2 with UU; an update every mean_every-th completed step
+  long mean_steps = 0, n_mean_updates = 0;             // completed steps since set/reset; updates since set
+  std::vector<float> mean_t;                           // meanflow.t
+  hipStream_t mean_stream = nullptr;                   // the stream the last update or reset went to (wl_sim_set_meanflow waits for it before it frees)
+  float* mean_P() const { return mean_own; }
+  float* mean_U() const { return mean_own ? mean_own + (size_t)G.cs : nullptr; }
+  float* mean_UU() const { return mean_own && mean_mode == 2 ? mean_own + (size_t)G.cs * (size_t)(1 + d.D) : nullptr; }
+  size_t mean_floats(int mode) const { return (size_t)G.cs * (size_t)(1 + d.D + (mode == 2 ? wl::meanflow_packed_planes(d.D) : 0)); }
+  void free_mean() { if (mean_own) (void)hipFree(mean_own); mean_own = nullptr; mean_mode = 0; mean_every = 1; mean_steps = 0; mean_t.clear(); }
+  bool mean_due() const { return mean_mode && (mean_steps + 1) % mean_every == 0; }      // the step now running (or the next one) ends with an update
+  float time_f(size_t n_dt) const { float t = 0.f; for (size_t k = 0; k < n_dt; k++) t += dt[k]; return t; }      // Float32, in order: sum(Δt[1:n])
+  int mean_reset(float t_init, hipStream_t s) {        // reset!(meanflow; t_init) :229-234
+    WL_HIP(hipMemsetAsync(mean_own, 0, mean_floats(mean_mode) * sizeof(float), s));
+    mean_t.assign(1, t_init); mean_steps = 0; mean_stream = s;
+    return 0;
+  }
+  int mean_update(float t_flow, hipStream_t s) {       // update!(meanflow, flow) :236-248 with time(flow) = t_flow; p is current (the callers see to that)
+    const float dtm = t_flow - mean_t.back();
+    float e = dtm / (dtm + (mean_t.back() - mean_t.front()) + 1.1920929e-7f);
+    if (mean_t.size() == 1) e = 1.f;                   // the first update takes the instantaneous field
+    WL_TRY(wl::meanflow_observe(mean_P(), mean_U(), mean_UU(), p, u, G, e, s));
+    mean_t.push_back(mean_t.back() + dtm);
+    n_mean_updates++; mean_stream = s;
+    return 0;
+  }
   void free_tracers() { if (tr_x) (void)hipFree(tr_x); if (tr_x0) (void)hipFree(tr_x0); tr_x = tr_x0 = nullptr; tr_n = 0; }
   int observe(hipStream_t s) {      // dt.back() is still the Δt this step ran with: cfl appends the next one afterwards
     if (probe_m) {
@@ -738,6 +769,14 @@ struct wl_sim {
       }
     }
     if (tr_n) WL_TRY(wl::advect(tr_x, tr_x0, u0, u, G, tr_n, dt.back(), d.perdir_mask, s));
+    if (mean_mode) {
+      const bool due = mean_due();
+      mean_steps++;
+      if (due) {
+        WL_TRY(materialise_p(s));   // (guard, as above)
+        WL_TRY(mean_update(time_f(dt.size()), s));
+      }
+    }
     return 0;
   }
   int mom_step(hipStream_t s, bool more_follow = false) {
@@ -1071,6 +1110,8 @@ int wl_sim_counter(wl_sim* s, const char* name, long* out) {
   if (n == "probe_dropped") { *out = s->n_probe_dropped; return 0; }
   if (n == "force_records") { *out = s->force_n; return 0; }                       // force records held / refused by a full buffer / active tiles of the list in use
   if (n == "force_dropped") { *out = s->n_force_dropped; return 0; }
+  if (n == "mean_updates") { *out = s->n_mean_updates; return 0; }                 // updates of the mean-flow observer since wl_sim_set_meanflow / its period (0: off)
+  if (n == "mean_every") { *out = s->mean_mode ? s->mean_every : 0; return 0; }
   if (n == "force_tiles") { *out = s->force_on ? s->fband.n_active : s->fimm.n_active; return 0; }
   wl_set_error("unknown counter " + n); return WL_EINVAL;
 }
@@ -1372,6 +1413,51 @@ int wl_sim_set_tracers(wl_sim* s, const float* host_x, size_t n) {
   WL_HIP(hipMemcpy(s->tr_x0, host_x, nb, hipMemcpyHostToDevice));      // position⁰ = position until the first step
   s->tr_n = n;
   return 0;
+}
+static int mean_handle_ok(wl_sim* s, const char* who, int need_mode) {
+  WL_CHECK(s, "null wl_sim");
+  if (s->comm) { wl_set_error(std::string(who) + ": z-slab handles are not supported (single domain only)"); return WL_EINVAL; }
+  if (s->mean_mode < need_mode) { wl_set_error(std::string(who) + (need_mode == 2 ? ": the observer keeps no UU (wl_sim_set_meanflow mode 2)" : ": no mean-flow observer is set (wl_sim_set_meanflow)")); return WL_EINVAL; }
+  return 0;
+}
+int wl_sim_set_meanflow(wl_sim* s, int mode, int every, float t_init, void* st) {
+  WL_TRY(mean_handle_ok(s, "wl_sim_set_meanflow", 0));
+  WL_CHECK(mode >= 0 && mode <= 2, "wl_sim_set_meanflow: mode must be 0 (off), 1 (P, U) or 2 (P, U, UU)");
+  WL_CHECK(mode == 0 || every >= 1, "wl_sim_set_meanflow: every < 1");
+  if (s->mean_own) WL_HIP(hipStreamSynchronize(s->mean_stream));      // an update may still be in flight on the stream of the last step
+  s->free_mean(); s->n_mean_updates = 0;
+  if (mode == 0) return 0;
+  if (hipMalloc((void**)&s->mean_own, s->mean_floats(mode) * sizeof(float)) != hipSuccess) { s->mean_own = nullptr; s->free_mean(); wl_set_error("wl_sim_set_meanflow: hipMalloc failed for the averages"); return (int)hipErrorOutOfMemory; }
+  s->mean_mode = mode; s->mean_every = every;
+  const int rc = s->mean_reset(std::isnan(t_init) ? (float)wl_sim_time(s) : t_init, wl_stream(st));
+  if (rc != 0) s->free_mean();
+  return rc;
+}
+int wl_sim_meanflow_reset(wl_sim* s, float t_init, void* st) {
+  WL_TRY(mean_handle_ok(s, "wl_sim_meanflow_reset", 1));
+  return s->mean_reset(std::isnan(t_init) ? (float)wl_sim_time(s) : t_init, wl_stream(st));
+}
+int wl_sim_meanflow_update(wl_sim* s, void* st) {
+  WL_TRY(mean_handle_ok(s, "wl_sim_meanflow_update", 1));
+  WL_TRY(s->settle(wl_stream(st)));      // (guards: between calls neither the divisor nor BC! is pending)
+  return s->mean_update(s->time_f(s->dt.size() - 1), wl_stream(st));
+}
+float* wl_sim_meanflow(wl_sim* s, int which, size_t* n) {
+  if (!s || !s->mean_mode || which < 0 || which > 2 || (which == 2 && s->mean_mode != 2)) return nullptr;
+  const size_t cs = (size_t)s->G.cs;
+  if (n) *n = cs * (size_t)(which == 0 ? 1 : which == 1 ? s->d.D : wl::meanflow_packed_planes(s->d.D));
+  return which == 0 ? s->mean_P() : which == 1 ? s->mean_U() : s->mean_UU();
+}
+int wl_sim_meanflow_uu(wl_sim* s, float* out, int tau, void* st) {
+  WL_TRY(mean_handle_ok(s, "wl_sim_meanflow_uu", 2));
+  WL_CHECK(out, "wl_sim_meanflow_uu: null output");
+  return wl::meanflow_expand(out, s->mean_UU(), s->mean_U(), s->G, tau, wl_stream(st));
+}
+int wl_sim_meanflow_t(const wl_sim* s, float* out, int cap) {
+  if (!s) return 0;
+  const int n = (int)s->mean_t.size();
+  for (int k = 0; k < n && k < cap && out; k++) out[k] = s->mean_t[(size_t)k];
+  return n;
 }
 float* wl_sim_tracers(wl_sim* s, int which, size_t* n) {
   if (!s || (which != 0 && which != 1)) return nullptr;

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import core
-from ._lib import check, lib, wl_grid, wl_sim_desc
+from ._lib import WlError, check, lib, wl_grid, wl_sim_desc
 from .core import perdir_mask, ptr, stream
 from .flow import Flow, mom_step_
 from .poisson import MultiLevelPoisson
@@ -367,7 +367,7 @@ class FusedSimulation:
         check(lib().wl_sim_set_option(self._h, name.encode(), int(value)))
 
     def counter(self, name):
-        """path counters of the handle (include/wlhip_bench.h wl_sim_counter): "resjac", "resjac_redo", "resjac_backoff", "xdefer", "tailfuse", "bcdefer", "pdefer", "tailwide", "rskip", "rskip_redo", "tailspec", "tailspec_armed", "launches", "probe_records", "probe_dropped", "force_records", "force_dropped", "force_tiles"; "tailfuse_min" reads the size gate of "tailfuse" in force;
+        """path counters of the handle (include/wlhip_bench.h wl_sim_counter): "resjac", "resjac_redo", "resjac_backoff", "xdefer", "tailfuse", "bcdefer", "pdefer", "tailwide", "rskip", "rskip_redo", "tailspec", "tailspec_armed", "launches", "probe_records", "probe_dropped", "force_records", "force_dropped", "force_tiles", "mean_updates", "mean_every"; "tailfuse_min" reads the size gate of "tailfuse" in force;
         with a body: "hybrid", "body_tile", "mask_valid", "part", "part_za", "part_zb" and the mask census "mask_near", "mask_needf_only", "mask_m0var_only",
         "mask_clean_in_box", "dirty_z0", "dirty_z1", "near_b0", "near_b1", "near_k0", "near_k1" """
         v = C.c_long(0)
@@ -627,6 +627,70 @@ class FusedSimulation:
                 __cuda_array_interface__ = {"shape": (cnt,), "typestr": "<f4", "data": (addr, False), "version": 2}
             out.append(torch.as_tensor(_Mem(), device=core.device()).view(int(n.value), self.D))
         return out[0], out[1]
+
+    def set_meanflow(self, uu_stats=False, every=1, t_init=None):
+        """MeanFlow(flow; t_init=time(flow), uu_stats) as an observer of this handle (src/Metrics.jl:205-226): after every `every`-th completed step —
+        mom_step_ and each step inside mom_steps_ — update! runs on the device in one launch, with no host round trip and the other steps' deferrals
+        left alone.  set_meanflow(None) switches it off and frees the averages."""
+        if uu_stats is None:
+            check(lib().wl_sim_set_meanflow(self._h, 0, 1, 0.0, stream()))
+            return
+        if int(every) < 1:
+            raise ValueError("every must be at least 1")
+        check(lib().wl_sim_set_meanflow(self._h, 2 if uu_stats else 1, int(every), float("nan") if t_init is None else float(t_init), stream()))
+
+    def reset_meanflow(self, t_init=0.0):
+        """reset!(meanflow; t_init)   :229-234"""
+        check(lib().wl_sim_meanflow_reset(self._h, float(t_init), stream()))
+
+    def update_meanflow(self):
+        """update!(meanflow, flow) now, on the current u and p (independent of `every`)   :236-248"""
+        check(lib().wl_sim_meanflow_update(self._h, stream()))
+
+    def _mean_view(self, which, shape):
+        import torch
+        n = C.c_size_t(0)
+        p = lib().wl_sim_meanflow(self._h, which, C.byref(n))
+        if not p:
+            raise WlError("no mean-flow observer is set (set_meanflow)" if which < 2 else "the mean-flow observer keeps no UU (set_meanflow(uu_stats=True))")
+        cnt, addr = int(np.prod(shape)), int(p)
+        assert cnt == int(n.value)
+
+        class _Mem:      # __cuda_array_interface__ of memory the handle owns
+            __cuda_array_interface__ = {"shape": (cnt,), "typestr": "<f4", "data": (addr, False), "version": 2}
+        t = torch.as_tensor(_Mem(), device=core.device())
+        return t.view(tuple(reversed(shape))).permute(*reversed(range(len(shape))))
+
+    def _mean_uu(self, tau):
+        if not lib().wl_sim_meanflow(self._h, 2, None):
+            raise WlError("the mean-flow observer keeps no UU (set_meanflow(uu_stats=True))")
+        out = core.jl_zeros(self.Ng + (self.D, self.D))
+        check(lib().wl_sim_meanflow_uu(self._h, ptr(out), int(tau), stream()))
+        return out
+
+    def meanflow_t(self):
+        """meanflow.t as a list of Float32"""
+        k = lib().wl_sim_meanflow_t(self._h, None, 0)
+        out = (C.c_float * max(k, 1))()
+        lib().wl_sim_meanflow_t(self._h, out, k)
+        return [np.float32(v) for v in out[:k]]
+
+    def meanflow(self):
+        """(P, U, UU, t): P and U are device tensors over the handle's memory in the shapes of field("p") and field("u") (valid until the next
+        set_meanflow); UU is a NEW (N…, D, D) device tensor expanded from the packed upper triangle the handle keeps, None without uu_stats; t = meanflow.t"""
+        P, U = self._mean_view(0, self.Ng), self._mean_view(1, self.Ng + (self.D,))
+        UU = self._mean_uu(0) if lib().wl_sim_meanflow(self._h, 2, None) else None
+        return P, U, UU, self.meanflow_t()
+
+    def meanflow_uu(self):
+        """uu(meanflow): the Reynolds stresses τ = UU − U⊗U as a new (N…, D, D) device tensor   :250-257"""
+        return self._mean_uu(1)
+
+    def load_meanflow_(self):
+        """copy!(flow, meanflow): flow.u .= U; flow.p .= P   :259-262"""
+        P, U, _, _ = self.meanflow()
+        self.set_field("u", core.to_host(U))
+        self.set_field("p", core.to_host(P))
 
     def sync(self):
         check(lib().wl_stream_sync(stream()))
