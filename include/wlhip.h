@@ -269,7 +269,22 @@ int wl_sim_init_flow(wl_sim* s, void* stream);          /* BC!(u), u⁰=u, μ₀
    "xdefer"[1] pair smoother: the V-cycle's x += ω·x_c↓ is applied by kernel B together with its own increment (x makes one round trip per smooth!)
    "tail_lds"[1] the single-launch coarse tail keeps r, x, ϵ of its levels in LDS (0: in global memory)
    "body_tile"[1] with a body: conv_diff!+BDIM! on the body-free plane ranges through the tiled NoBody kernel ("convt")
-   "itmx"[32] solver!'s iteration cap `itmx` (src/MultiLevelPoisson.jl:108) */
+   "rskip"[1] the pair smoother's kernel B does not store the residual nobody reads; needs the pair kernels ("fused_smoother", "pair", "constl") and stands down with
+       "store_eps", a periodic direction or a body (every coarse level's r, and the finest level's in the iteration at which the last solve of the same projection
+       of a step stopped: counted from the second step on; wl_mg_level_field brings that residual up to date when asked)
+   "resjac" for tests — 2 (tests): every head is redone through the two-kernel path, and "bcdefer", "pdefer" and "tailspec" are told so in advance and stand down;
+       3 (tests): the same, not announced: "bcdefer" and "pdefer" defer and are flushed before the two-kernel head; the gated tail is withheld
+   "itmx"[32] solver!'s iteration cap `itmx` (src/MultiLevelPoisson.jl:108)
+   Next to one another (tests/optmatrix.py restates these sentences and tests/test_gpu_optmatrix.py holds the path counters to them on every pair of switches):
+       the one-launch head needs the constant-coefficient kernels ("constl"), the fused projection ("fuse_p") and the folded mean shift ("defer_shift"), and does not
+       run with "store_f", a body, exitBC or a periodic direction; "pdefer", "bcdefer" and "tailspec" build on that head: they stand down wherever it does;
+       the gated tail is queued by the speculative first V-cycle: without "headspec", or where the one-launch head does not run, "tailspec" does nothing;
+       "bcfold": with bit 1 set, where the tiled kernel runs ("convt"), that kernel has applied BC! itself and "bcdefer" has nothing to defer; "convz" is not the
+       fused launch that "bcdefer" defers behind;
+       "tailfuse" needs the flux-once tiled launch ("convt", "convf"; not "convz", "convm"), the fused projection ("fuse_p"), constant coefficients ("constl"), a
+       folded BC! ("bcfold" not 0) and f not stored ("store_f"); "tailwide" needs the fused projection ("fuse_p") and the constant-coefficient kernels ("constl");
+       "xdefer" needs the pair kernels ("fused_smoother", "pair", "constl"); "body_tile" is a branch of the "hybrid" launch, taken for ranges of whole planes when
+       f is not stored.  Every switch not named for a path leaves it running. */
 int wl_sim_set_option(wl_sim* s, const char* name, int value);
 /* "resjac_min", "convt_min", "convt", "convf", "tail_lds", "body_tile", "pair", "jacobi_march", "convm" (and wl_mg_set_fused bits 2 and 5) are PROCESS-wide:
    they choose between kernels that produce identical bits, for every handle of the process.  wl_reset_process_options() restores their defaults. */

@@ -257,3 +257,27 @@ def test_rskip_switched_off_counts_nothing_and_stores(w, oracle):
     c = (on.counter("rskip"), on.counter("rskip_redo"))
     run_pair(w, on, off, (2, 0), "both off")
     assert (on.counter("rskip"), on.counter("rskip_redo")) == c
+
+
+@pytest.mark.parametrize("withdraw", ["pair", "constl"])
+def test_late_store_after_the_pair_kernels_were_switched_off(w, oracle, withdraw):
+    """found by tests/test_gpu_optmatrix.py (the walk, reduced): a solve ends on a skipped store, then "pair" (process-wide) or "constl" (update!) withdraws the
+    pair kernels, then somebody asks for r — set_option("rskip"), wl_mg_level_field.  The late store is the launch that skipped it, made again: it may not go
+    by today's switches (it returned WL_EINVAL: "storing only one of r' and x needs the pair kernel").  r equals the handle's that stored every time."""
+    u0 = random_u(oracle, SMALL, 3)
+    on, off = make(w, SMALL, u0), make(w, SMALL, u0, rskip=0)
+    for _ in range(6):                             # until a call ends on a skipped store (the corrector's solve stops where its last one did)
+        for s in (on, off):
+            s.mom_step_()
+        if policy(on.pois_n)[2]:
+            break
+    assert policy(on.pois_n)[2] and on.counter("rskip") > 0, (on.pois_n, "no solve of six steps ended on a skipped store")
+    for s in (on, off):
+        s.set_option(withdraw, 0)
+    r0 = on.counter("rskip_redo")
+    on.set_option("rskip", 0)                      # settles the debt before it switches
+    assert on.counter("rskip_redo") == r0 + 1
+    assert np.array_equal(bits(on.pois_level("r")), bits(off.pois_level("r")))
+    for s in (on, off):
+        s.mom_step_()
+    assert_same_state(on, off, withdraw)

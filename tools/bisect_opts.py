@@ -1,40 +1,60 @@
 #!/usr/bin/env python3
-"""which implementation switch makes a shape deviate from the plain path?  usage: tools/bisect_opts.py nx ny nz [nu] [Ux]"""
-import os, sys
-import numpy as np
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import waterlily_jl_amd as w
-dims = tuple(int(v) for v in sys.argv[1:4])
-nu = float(sys.argv[4]) if len(sys.argv) > 4 else 0.01
-U = (float(sys.argv[5]) if len(sys.argv) > 5 else 0.3, 0.0, 0.0)
-rng = np.random.default_rng(5)
-u0 = np.asfortranarray(rng.uniform(-0.5, 0.5, size=tuple(n + 2 for n in dims) + (3,)).astype(np.float32))
-PLAIN = {"fused_smoother": 0, "fuse_p": 0, "constl": 0, "fuse_cfl": 0, "store_f": 1, "tail": 0, "jacobi_march": 0}
-def run(opts, steps=2):
-    s = w.FusedSimulation(dims, U, dims[0], U=1, nu=nu, u0=u0)
-    for k, v in opts.items(): s.set_option(k, v)
-    out = []
-    for _ in range(steps):
-        s.mom_step_(); out.append((s.field("u"), s.field("p"), list(s.pois_n), float(s.dt[-1])))
-    return out
-ref = run(PLAIN)
-for name, val in (("fused_smoother", 1), ("fuse_p", 1), ("constl", 1), ("fuse_cfl", 1), ("store_f", 0), ("tail", 1), ("jacobi_march", 1)):
-    o = dict(PLAIN); o[name] = val
-    if name == "fuse_cfl": o["fuse_p"] = 1
-    if name == "jacobi_march": o["constl"] = 1
-    r = run(o)
-    for st in range(len(ref)):
-        du = float(np.abs(r[st][0] - ref[st][0]).max()); dp = float(np.abs(r[st][1] - ref[st][1]).max())
-        print(f"{name}={val} step {st}: du={du:.2e} dp={dp:.2e} n={r[st][2]} vs {ref[st][2]} dt={r[st][3]:.6f}/{ref[st][3]:.6f}")
-r = run({})
-for st in range(len(ref)):
-    du = float(np.abs(r[st][0] - ref[st][0]).max()); dp = float(np.abs(r[st][1] - ref[st][1]).max())
-    print(f"ALL FAST step {st}: du={du:.2e} dp={dp:.2e} n={r[st][2]} vs {ref[st][2]} dt={r[st][3]:.6f}/{ref[st][3]:.6f}")
-# pairs of options
-import itertools
-names = [("fused_smoother", 1), ("fuse_p", 1), ("constl", 1), ("store_f", 0), ("tail", 1)]
-for (a, va), (b, vb) in itertools.combinations(names, 2):
-    o = dict(PLAIN); o[a] = va; o[b] = vb
-    r = run(o, 1)
-    du = float(np.abs(r[0][0] - ref[0][0]).max())
-    if du != 0.0: print(f"{a}+{b}: du={du:.2e} n={r[0][2]} vs {ref[0][2]}")
+"""which implementation switches make a flow deviate from the plain path?  A front end to tests/optmatrix.py (the covering array of every pair of switches).
+
+usage: tools/bisect_opts.py FAMILY                 every pair row of the family against the PLAIN handle; the first row that deviates is shrunk
+       tools/bisect_opts.py FAMILY name=value ...  that row (switches not named: at their defaults) against PLAIN, shrunk if it deviates
+       tools/bisect_opts.py --rows FAMILY          print the rows (no GPU)
+FAMILY: box ragged periodic moving exit circle2d.  Never on a row that ended in a GPU fault or a hang."""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import optmatrix as om
+
+
+def main(argv):
+    if not argv or argv[0] in ("-h", "--help"):
+        print(__doc__)
+        return 2
+    list_rows = argv[0] == "--rows"
+    args = argv[1:] if list_rows else argv
+    if not args or args[0] not in om.FAMILIES or (list_rows and len(args) != 1):
+        print(__doc__)
+        return 2
+    family = args[0]
+    if list_rows:
+        for i, r in enumerate(om.pair_rows(family)):
+            print(i, {n: v for n, v in r.items() if v != om.FACTORS[n][0]}, "live:", sorted(om.live(r, family)))
+        return 0
+    if len(args) > 1:
+        row = om.defaults(om.names(family))
+        given = dict(a.split("=", 1) for a in args[1:] if "=" in a)
+        if len(given) != len(args) - 1 or not set(given) <= set(row):
+            print(__doc__)
+            return 2
+        row.update({k: int(v) for k, v in given.items()})
+        return 0 if om.shrink(family, row) == {} else 1
+    import waterlily_jl_amd as w
+    w.core.device()
+    try:
+        ref, _, err = om.run(family, w, {n: om.PLAIN[n] for n in om.names(family)})
+        assert err is None, err
+        for i, row in enumerate(om.pair_rows(family)):
+            w.lib().wl_reset_process_options()
+            snaps, cnt, err = om.run(family, w, row)
+            d = om.first_diff(snaps, ref) if err is None else None
+            faults = om.counter_faults(row, family, cnt)
+            print("row %2d %s %s" % (i, "error: " + err if err else ("differs: %r" % (d[:3],) if d else "same bits"), "; ".join(faults)))
+            if err:
+                return 1
+            if d:
+                om.shrink(family, row, w)
+                return 1
+    finally:
+        w.lib().wl_reset_process_options()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))

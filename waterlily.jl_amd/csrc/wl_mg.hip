@@ -138,7 +138,9 @@ int wl_mg::settle_r(hipStream_t s) {
   if (!r_stale) return 0;
   Level& p = lv[0];
   r_stale = false; n_rskip_redo++;
-  return wl::gsrb_fused_B(nullptr, p.r, p.x, p.em, p.rs, p.L, p.x_, r_stale_w, nullptr, WL_RD_L1, WL_RF_LINF, p.cl, s, nullptr, wl::B_RONLY);
+  // the pair kernel itself, with the coefficients of the launch that skipped the store — not gsrb_fused_B's choice of today: the process-wide "pair" switch or
+  // "constl" (update!) may have withdrawn the pair kernels since, and only they store r' alone
+  return wl::gsrb_pair_B(nullptr, p.r, p.x, p.em, p.rs, p.x_, r_stale_w, nullptr, WL_RD_L1, WL_RF_LINF, r_stale_cl, s, nullptr, wl::B_RONLY);
 }
 // … for a reader that names no stream: behind the launch that skipped the store, on its stream (stream 0 if that stream is gone), and complete on return —
 // whichever stream the caller then reads r on finds it current
@@ -188,7 +190,7 @@ int wl_mg::smooth(int l, int it, float w, hipStream_t s, bool want_norms, bool* 
   if (plan.form == Smooth::ZSplit && want_norms) { ZPart parts[3]; zsplit_parts(*this, p, parts); for (int i = 0; i < 3; i++) if (parts[i].any()) norm_slots |= 1 << i; }
   if (norms_done) *norms_done = want_norms;
   if (l == 0 && plan.pro) last_xdefer = plan.xdefer ? 1 : 0;
-  if (l == 0 && plan.bout == wl::B_XONLY) { r_stale = true; r_stale_w = w; r_stale_stream = s; n_rskip++; }
+  if (l == 0 && plan.bout == wl::B_XONLY) { r_stale = true; r_stale_w = w; r_stale_stream = s; r_stale_cl = p.cl; n_rskip++; }
   return 0;
 }
 // kernel B of the level, or of the plane range g of it.  coarse (a prolongation was absorbed): kernel A's extra stage left r' in p.rs and B stores the final

@@ -45,6 +45,7 @@ struct wl_mg {
   int rskip_hist[2] = {0, 0};      // iterations of the last solve that stood, per slot (0: none yet — store)
   bool r_stale = false; float r_stale_w = 0.f;      // lv[0].r was not written by the last smooth!(0): kernel B's inputs lv[0].em, lv[0].rs are intact, ω as given
   hipStream_t r_stale_stream = nullptr;             // … and the stream that launch ran on: where a stream-less reader (wl_mg_level_field) has r produced, and waits for it
+  wl::ConstL r_stale_cl{};                          // … and the coefficients it ran with: the late store is that pair kernel again, whatever "pair" or "constl" have been set to since
   long n_rskip = 0, n_rskip_redo = 0;      // finest-level launches that skipped the store / r-only launches (lazy ones included)
   int settle_r(hipStream_t s);
   int settle_r_for_reader();
