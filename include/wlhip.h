@@ -181,7 +181,9 @@ int wl_mg_set_fused(wl_mg* mg, int on);   /* bit0 (default 1): temporally blocke
                                              bit1: do not store the final ϵ (scratch of the reference that nothing reads again);
                                              bit2: no pair kernels; bit3: no single-launch coarse tail; bit4: no z-split on body levels;
                                              bit5: coarse tail in global memory instead of LDS (process-wide switch); bit6: x increment of the prolongation not deferred to kernel B;
-                                             bit7: z-slabs: the smoother's deep r exchange is not overlapped with kernel A's interior planes */
+                                             bit7: z-slabs: the smoother's deep r exchange is not overlapped with kernel A's interior planes;
+                                             bit8: the pair smoother's kernels A and B exchange r′ and ϵ_mid through the two dense arrays only, never through the
+                                             level's line-aligned exchange buffer (which needs bit1 set, bit6 clear and a pending prolongation: Vcycle! inside solver!) */
 /* solver!(ml;tol,itmx): returns iterations in *host_n and the last L₁/L∞; appends to the n history. */
 int wl_mg_solve(wl_mg* mg, double tol, int itmx, int* host_n, double* host_r1, float* host_rinf, void* stream);
 int wl_mg_history(const wl_mg* mg, int16_t* host_out, int cap);                        /* pois.n :66 */
@@ -267,6 +269,9 @@ int wl_sim_init_flow(wl_sim* s, void* stream);          /* BC!(u), u⁰=u, μ₀
    "convf"[1] the tiled conv_diff!+BDIM! evaluates every face flux once (wl_convf.hip); 0: the two-cells-per-thread kernel that re-evaluates upper faces
    "convt_min"[2048] tile-planes below which "convt" leaves the launch to the plane kernel (tests: 0)
    "xdefer"[1] pair smoother: the V-cycle's x += ω·x_c↓ is applied by kernel B together with its own increment (x makes one round trip per smooth!)
+       — and, at value 1, kernel A then hands its r′ and ϵ_mid to kernel B as one 16-byte element per cell pair through a line-aligned buffer of the level
+       (csrc/wl_abwide.hpp) instead of two dense arrays: single-domain levels without "store_eps", a periodic direction or a body, in the smooth! that absorbs a
+       prolongation; 2: the deferred increment with the two dense arrays.  Same bits either way (wl_sim_counter: finest-level smooth! calls that took the buffer)
    "tail_lds"[1] the single-launch coarse tail keeps r, x, ϵ of its levels in LDS (0: in global memory)
    "body_tile"[1] with a body: conv_diff!+BDIM! on the body-free plane ranges through the tiled NoBody kernel ("convt")
    "rskip"[1] the pair smoother's kernel B does not store the residual nobody reads; needs the pair kernels ("fused_smoother", "pair", "constl") and stands down with

@@ -39,6 +39,8 @@ int wl_placement_scores(double* out, int cap);
  * "tailfuse_min" = no count: the size gate of that path in force on this handle (interior cells; option "tailfuse_min"),
  * "xdefer" = what the finest level's last smooth! decided: 1 the V-cycle's x += ω·x_c↓ was applied by smoother kernel B, 0 by kernel A, −1 none yet
  * (decides which bytes bench.py books to kernels A and B),
+ * "abwide" = finest-level smooth! calls in which kernel A handed r′ and ϵ_mid to kernel B through the level's exchange buffer (one float4 per cell pair,
+ * csrc/wl_abwide.hpp) instead of the two dense arrays,
  * flows with a body — which body-aware path ran: "hybrid" = predict/correct calls that took the body-aware conv_diff!+BDIM! (two per step where live),
  * "body_tile" = tiled far-range launches of that path (PROCESS-wide, like the option: read it as a difference), "mask_valid" = 1 while the masks of the last
  * measure!/update! are in force (0 after wl_sim_field handed out V, mu0 or mu1), "part" / "part_za" / "part_zb" = the finest level runs the z-split smoother /

@@ -385,13 +385,13 @@ int pcg_stage(int stage, float* eps, float* r, float* x, float* z, const float* 
 bool gsrb_fused_ok(const GridX& g, unsigned per, bool dist);
 int gsrb_fused_A(float* emid, const float* r, const float* L, const GridX& g, const ConstL& cl, hipStream_t s);
 int gsrb_fused_A_pro(float* emid, float* rnew, float* x, const float* r, const float* xc, const float* L, const GridX& g, const GridX& gc, float w, const ConstL& cl, hipStream_t s,
-                     int xk0 = -(1 << 30), int xk1 = 1 << 30, bool* defer_x = nullptr, bool range = false);   // defer_x (in/out): leave `x += ω·x_c↓` to kernel B (cleared if this path cannot); range: g is a short plane sub-range of a qualifying level
+                     int xk0 = -(1 << 30), int xk1 = 1 << 30, bool* defer_x = nullptr, bool range = false, float* wide = nullptr);   // defer_x (in/out): leave `x += ω·x_c↓` to kernel B (cleared if this path cannot); range: g is a short plane sub-range of a qualifying level; wide: r′ and ϵ_mid go to this exchange buffer (wl_abwide.hpp) instead of rnew and emid — needs the pair kernel and *defer_x
 // The V-cycle's `x += ω·x_c↓` handed from kernel A to kernel B of the same smooth! (pair kernels only): A leaves x alone, B applies both
 // increments of x in order — x is read and written once per smooth! instead of twice.
 struct XDefer { const float* xc; GridX gc; float w; };
 bool gsrb_pair_B_ok(const float* eps, const float* rout, const float* x, const float* emid, const float* r, const GridX& g, const ConstL& cl);
 int gsrb_fused_B(float* eps, float* rout, float* x, const float* emid, const float* r, const float* L, const GridX& g, float w,
-                 const RedWs* ws, int slot_d, int slot_f, const ConstL& cl, hipStream_t s, const XDefer* xd = nullptr, int out = 0);   // xd, out ≠ 0 (wl::BOut): only when gsrb_pair_B_ok
+                 const RedWs* ws, int slot_d, int slot_f, const ConstL& cl, hipStream_t s, const XDefer* xd = nullptr, int out = 0, const float* wide = nullptr);   // xd, out ≠ 0 (wl::BOut), wide: only when gsrb_pair_B_ok
 int finalize_sum_max(const RedWs& ws, int nparts, int slot_d, int slot_f, hipStream_t s);
 // pair variant of the blocked smoother for constant-coefficient levels (wl_fused2.hip); chosen inside gsrb_fused_* when eligible
 void gsrb_pair_enable(int on);
@@ -400,12 +400,15 @@ bool gsrb_pair_ok_range(const GridX& g, const ConstL& cl);
 bool gsrb_pair_geom_ok(const GridX& g);
 int gsrb_pair_A(float* emid, const float* r, const GridX& g, const ConstL& cl, hipStream_t s);
 int gsrb_pair_A_pro(float* emid, float* rnew, float* x, const float* r, const float* xc, const GridX& g, const GridX& gc, float w, const ConstL& cl, hipStream_t s,
-                    int xk0 = -(1 << 30), int xk1 = 1 << 30);   // [xk0,xk1): planes on which x is updated (default: every output plane)
+                    int xk0 = -(1 << 30), int xk1 = 1 << 30, float* wide = nullptr);   // [xk0,xk1): planes on which x is updated (default: every output plane)
+// The exchange buffer W of a level (wl_abwide.hpp): kernel A's wide form (`wide`, with an empty [xk0,xk1)) writes r′ and ϵ_mid there as one float4 per pair and
+// leaves rnew, emid and x alone; kernel B's wide form reads them from there (its emid and r are then ignored; no eps).  Bytes of W for a level, 0: not for this one
+size_t gsrb_pair_wide_bytes(const GridX& g);
 // which of increment!'s results kernel B of the pair smoother stores: both (default) | x only — rout is not written, and since the launch leaves its inputs
 // ϵ_mid and r alone, | r only with the same arguments produces rout afterwards, bit for bit (neither loads nor stores x, no norms)
 enum BOut { B_BOTH = 0, B_XONLY = 1, B_RONLY = 2 };
 int gsrb_pair_B(float* eps, float* rout, float* x, const float* emid, const float* r, const GridX& g, float w,
-                const RedWs* ws, int slot_d, int slot_f, const ConstL& cl, hipStream_t s, const XDefer* xd = nullptr, int out = B_BOTH);
+                const RedWs* ws, int slot_d, int slot_f, const ConstL& cl, hipStream_t s, const XDefer* xd = nullptr, int out = B_BOTH, const float* wide = nullptr);
 bool gsrb_pair_B_kernel_norms(const GridX& g);   // a launch with ws takes the norms from registers (else: from the stored rout — B_XONLY is refused)
 int restrict_(float* a, const GridX& gc, const float* b, const GridX& gf, hipStream_t s);
 int prolongate(float* a, const GridX& gf, const float* b, const GridX& gc, hipStream_t s);

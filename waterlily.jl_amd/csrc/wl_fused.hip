@@ -326,11 +326,13 @@ int gsrb_fused_A(float* emid, const float* r, const float* L, const GridX& g, co
 }
 // prolongate!+increment!(ω) of the V-cycle folded into kernel A: r' -> rnew (≠ r), x updated in place, ϵ_mid from r'
 int gsrb_fused_A_pro(float* emid, float* rnew, float* x, const float* r, const float* xc, const float* L, const GridX& g, const GridX& gc, float w, const ConstL& cl, hipStream_t s,
-                     int xk0, int xk1, bool* defer_x, bool range) {
+                     int xk0, int xk1, bool* defer_x, bool range, float* wide) {
   if ((range ? gsrb_pair_ok_range(g, cl) : gsrb_pair_ok(g, cl)) && gc.cs < (1L << 30) && al8(emid, rnew, x, r)) {
     if (defer_x && *defer_x) { xk0 = 0; xk1 = 0; }    // x is left to kernel B (wl::XDefer)
-    return gsrb_pair_A_pro(emid, rnew, x, r, xc, g, gc, w, cl, s, xk0, xk1);
+    if (wide && !(defer_x && *defer_x && !range)) { wl_set_error("gsrb_fused_A_pro: the wide exchange needs the deferred x increment on a whole level"); return WL_EINVAL; }
+    return gsrb_pair_A_pro(emid, rnew, x, r, xc, g, gc, w, cl, s, xk0, xk1, wide);
   }
+  if (wide) { wl_set_error("gsrb_fused_A_pro: the wide exchange needs the pair kernel"); return WL_EINVAL; }
   if (defer_x) *defer_x = false;
   if (g.nz != g.gnz) { wl_set_error("blocked smoother on a z-slab level needs the pair kernels"); return WL_EINVAL; }
   const int zc = zchunk_for(g, 2);
@@ -346,8 +348,9 @@ bool gsrb_pair_B_ok(const float* eps, const float* rout, const float* x, const f
   return gsrb_pair_ok(g, cl) && al8(eps, rout, x, emid, r);
 }
 int gsrb_fused_B(float* eps, float* rout, float* x, const float* emid, const float* r, const float* L, const GridX& g, float w,
-                 const RedWs* ws, int slot_d, int slot_f, const ConstL& cl, hipStream_t s, const XDefer* xd, int out) {
-  if (gsrb_pair_B_ok(eps, rout, x, emid, r, g, cl)) return gsrb_pair_B(eps, rout, x, emid, r, g, w, ws, slot_d, slot_f, cl, s, xd, out);
+                 const RedWs* ws, int slot_d, int slot_f, const ConstL& cl, hipStream_t s, const XDefer* xd, int out, const float* wide) {
+  if (gsrb_pair_B_ok(eps, rout, x, emid, r, g, cl)) return gsrb_pair_B(eps, rout, x, emid, r, g, w, ws, slot_d, slot_f, cl, s, xd, out, wide);
+  if (wide) { wl_set_error("gsrb_fused_B: the wide exchange needs the pair kernel"); return WL_EINVAL; }
   if (out != B_BOTH) { wl_set_error("gsrb_fused_B: storing only one of r' and x needs the pair kernel"); return WL_EINVAL; }
   if (xd) { wl_set_error("gsrb_fused_B: a deferred x increment needs the pair kernel"); return WL_EINVAL; }
   if (g.nz != g.gnz) { wl_set_error("blocked smoother on a z-slab level needs the pair kernels"); return WL_EINVAL; }

@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "wl_common.hpp"
+#include "wl_abwide.hpp"
 
 int g_pair_on = 1;
 int g_pro_fast = 1;   // bit 1 of gsrb_pair_enable: register-window prolongation when every direction is coarsened
@@ -62,13 +63,23 @@ static bool rows16(const GridX& g, int kernel = 0) {   // kernel: 1 = A, 2 = B (
 int gsrb_pair_A(float* emid, const float* r, const GridX& g, const ConstL& cl, hipStream_t s) {
   return rows16(g, 1) ? pair16::gsrb_pair_A(emid, r, g, cl, s) : pair32::gsrb_pair_A(emid, r, g, cl, s);
 }
-int gsrb_pair_A_pro(float* emid, float* rnew, float* x, const float* r, const float* xc, const GridX& g, const GridX& gc, float w, const ConstL& cl, hipStream_t s, int xk0, int xk1) {
-  return rows16(g, 1) ? pair16::gsrb_pair_A_pro(emid, rnew, x, r, xc, g, gc, w, cl, s, xk0, xk1) : pair32::gsrb_pair_A_pro(emid, rnew, x, r, xc, g, gc, w, cl, s, xk0, xk1);
+int gsrb_pair_A_pro(float* emid, float* rnew, float* x, const float* r, const float* xc, const GridX& g, const GridX& gc, float w, const ConstL& cl, hipStream_t s, int xk0, int xk1, float* wide) {
+  return rows16(g, 1) ? pair16::gsrb_pair_A_pro(emid, rnew, x, r, xc, g, gc, w, cl, s, xk0, xk1, wide) : pair32::gsrb_pair_A_pro(emid, rnew, x, r, xc, g, gc, w, cl, s, xk0, xk1, wide);
+}
+// Bytes of the exchange buffer W of a single-domain level (wl_abwide.hpp), 0 if the level cannot use one: the geometry of the pair kernels (whatever the "pair"
+// switch says today), and the bound the kernels' descriptors over W rest on — the planes of one z-chunk (+ kernel B's halo planes) within 2^30 bytes, so that a
+// flagged "no access" offset (WL_OOB_LANE = 2^30 and up) is out of range whichever in-range plane offset is added to it, and every 32-bit offset sum is exact.
+size_t gsrb_pair_wide_bytes(const GridX& g) {
+  if (!(g.D == 3 && (g.nx & 1) == 0 && g.nx >= pair_min_nx() && g.ny >= 34 && g.gnz >= 10 && (g.k1 - g.k0) >= 8 && g.nz == g.gnz && g.gk == 0 && g.cs < (1L << 30))) return 0;
+  const size_t wpl = (size_t)g.ny * abw_pitch(g.nx);
+  const int a = pair16::wide_chunk_planes(g), b = pair32::wide_chunk_planes(g);
+  if ((size_t)((a > b ? a : b) + 8) * wpl > ((size_t)1 << 30)) return 0;
+  return wpl * (size_t)g.nz;
 }
 int gsrb_pair_B(float* eps, float* rout, float* x, const float* emid, const float* r, const GridX& g, float w,
-                const RedWs* ws, int slot_d, int slot_f, const ConstL& cl, hipStream_t s, const XDefer* xd, int out) {
+                const RedWs* ws, int slot_d, int slot_f, const ConstL& cl, hipStream_t s, const XDefer* xd, int out, const float* wide) {
   if (xd && xd->gc.cs >= (1L << 30)) { wl_set_error("gsrb_pair_B: coarse level too large for 32-bit offsets"); return WL_EINVAL; }
-  return rows16(g, 2) ? pair16::gsrb_pair_B(eps, rout, x, emid, r, g, w, ws, slot_d, slot_f, cl, s, xd, out) : pair32::gsrb_pair_B(eps, rout, x, emid, r, g, w, ws, slot_d, slot_f, cl, s, xd, out);
+  return rows16(g, 2) ? pair16::gsrb_pair_B(eps, rout, x, emid, r, g, w, ws, slot_d, slot_f, cl, s, xd, out, wide) : pair32::gsrb_pair_B(eps, rout, x, emid, r, g, w, ws, slot_d, slot_f, cl, s, xd, out, wide);
 }
 bool gsrb_pair_B_kernel_norms(const GridX& g) { return rows16(g, 2) ? pair16::gsrb_pair_B_kernel_norms(g) : pair32::gsrb_pair_B_kernel_norms(g); }
 }  // namespace wl

@@ -147,6 +147,30 @@ __device__ __forceinline__ void bst2(__amdgpu_buffer_rsrc_t b, unsigned voff, un
   wl_v2u t; t.x = __float_as_uint(v.x); t.y = __float_as_uint(v.y);
   __builtin_amdgcn_raw_buffer_store_b64(t, b, (int)voff, (int)soff, 0);
 }
+// 16-byte forms for the exchange buffer W (wl_abwide.hpp).  W may exceed the 2^30 bytes the flags above assume, so a workgroup's descriptor covers only the
+// planes of its own z-chunk: base = the chunk's first plane, num_records = those planes (gsrb_pair_wide_bytes bounds them by 2^30: a flagged offset is then
+// >= num_records whatever in-range plane offset is added, and a valid lane offset + plane offset stays below num_records)
+typedef unsigned wl_v4u __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mkbufw(const float* p, size_t byte0, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p)) + byte0, 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ float4 bld4(__amdgpu_buffer_rsrc_t b, unsigned voff, unsigned soff) {
+  const wl_v4u t = __builtin_amdgcn_raw_buffer_load_b128(b, (int)voff, (int)soff, 0);
+  return make_float4(__uint_as_float(t.x), __uint_as_float(t.y), __uint_as_float(t.z), __uint_as_float(t.w));
+}
+__device__ __forceinline__ void bst4(__amdgpu_buffer_rsrc_t b, unsigned voff, unsigned soff, float4 v) {
+  wl_v4u t; t.x = __float_as_uint(v.x); t.y = __float_as_uint(v.y); t.z = __float_as_uint(v.z); t.w = __float_as_uint(v.w);
+  __builtin_amdgcn_raw_buffer_store_b128(t, b, (int)voff, (int)soff, 0);
+}
+__device__ __forceinline__ float4 ldw(const float* __restrict__ W, size_t bo) { return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(W) + bo); }
+__device__ __forceinline__ void stw(float* __restrict__ W, size_t bo, float4 v) { *reinterpret_cast<float4*>(reinterpret_cast<char*>(W) + bo) = v; }
+// kernel A's wide store: 1 — every lane of a stored tile row stores, the two halo lanes (and lanes beyond the array) zeros into padding slots, so a wave row is one
+// whole 512-byte burst; 0 — only the lanes that own a pair store.  Measured per instance (profiles/abwide_experiments.md §4): the burst wins on the 32-row
+// instance (512² planes: A 479 -> 418 µs), the plain form on the 16-row one (258² planes: 67 -> 58 µs — the last segment of a 258-cell row is 70 % padding)
+#ifndef WL_ABW_PAD
+#define WL_ABW_PAD (PT_Y == 32)
+#endif
+static_assert(2 * PT_X - 4 == wl::ABW_CX, "a segment of W is a core column of kernel A");
 // timing ablations (experiments; wrong results): -DWL_ABL_NOSTORE drops every store of the fast steps, -DWL_ABL_NOLOAD every load,
 // -DWL_ABL_NOBAR removes the fast steps' barrier
 #ifdef WL_ABL_NOSTORE
@@ -191,7 +215,9 @@ __device__ __forceinline__ int dwn(int i, int c) { return c ? (i + 1) / 2 : i; }
 // kernel A:  [PRO: r' = r − ω·A(x_c↓), x += ω·x_c↓  (Vcycle!'s prolongate!+increment!, src/MultiLevelPoisson.jl:99-100)]
 //            ϵ = r·iD ; colour sweep 1 ; colour sweep 2  →  ϵ_mid
 // ------------------------------------------------------------------------------------------------------------------
-template <int PRO>
+// WIDE (only with PRO, and only when x is left to kernel B): `emid` is the level's exchange buffer W.  r′ and ϵ_mid of plane K−2 leave together, as one 16-byte
+// store at step K (r′ of that plane is still in r2); rnew, x and the dense emid are not touched.
+template <int PRO, int WIDE = 0>
 __global__ void __launch_bounds__(PT_N, WL_A_WAVES) k_gsrb2_A(GridX g, float* __restrict__ emid, const float* __restrict__ r, int zchunk, ProArgs2 pa, wl::ConstL cl) {
   __shared__ float sA[2][PL_SZ];   // ϵ⁰ of the newest plane
   __shared__ float sB[2][PL_SZ];   // plane K-1 after sweep 1
@@ -236,7 +262,7 @@ __global__ void __launch_bounds__(PT_N, WL_A_WAVES) k_gsrb2_A(GridX g, float* __
     const bool pl0 = t.indom && pint(g, K);                     // r of ghost planes/cells is 0
     const unsigned o = t.oc + (unsigned)K * (unsigned)g.sz;
     n_r0 = pl0 ? ld2(r, o) : make_float2(0.f, 0.f);
-    if (PRO) n_x0 = ((t.st0 || t.st1) && K >= t.ks && K < t.ke && K >= pa.xk0 && K < pa.xk1) ? ld2(pa.x, o) : make_float2(0.f, 0.f);
+    if (PRO && !WIDE) n_x0 = ((t.st0 || t.st1) && K >= t.ks && K < t.ke && K >= pa.xk0 && K < pa.xk1) ? ld2(pa.x, o) : make_float2(0.f, 0.f);
     if (PRO == 2) {   // coarse values that become current at step K: plane m(K-1)+1; own row if K is even, other row if odd
       const unsigned a = ((K & 1) ? ro : rc) + cpl((K >> 1) + 1);
       n_c = make_float2(pa.xc[a], pa.xc[a + 1]);
@@ -263,6 +289,17 @@ __global__ void __launch_bounds__(PT_N, WL_A_WAVES) k_gsrb2_A(GridX g, float* __
   const unsigned fbytes = (unsigned)(g.cs * 4);
   const __amdgpu_buffer_rsrc_t b_r = mkbuf(r, WL_LDBYTES(fbytes)), b_x = mkbuf(pa.x, WL_LDBYTES(fbytes)), b_xs = mkbuf(pa.x, WL_STBYTES(fbytes)), b_rn = mkbuf(pa.rnew, WL_STBYTES(fbytes)), b_em = mkbuf(emid, WL_STBYTES(fbytes));
   const unsigned vst = stp ? ob0 : WL_OOB_LANE;                    // store offset of the lane (tile core ∧ interior), else out of range
+  // WIDE: bytes per plane of W, the pair's offset inside a plane, the chunk's descriptor (planes [ks,ke): the ones this workgroup stores) and the lane's store offset
+  const unsigned wpl = WIDE ? (unsigned)g.ny * wl::abw_pitch(g.nx) : 0u;
+  const unsigned wo = (WIDE && t.indom) ? (unsigned)t.j * wl::abw_pitch(g.nx) + wl::abw_slot(t.i0) : 0u;
+  const __amdgpu_buffer_rsrc_t b_w = mkbufw(emid, WIDE ? (size_t)t.ks * wpl : 0, WIDE ? WL_STBYTES((unsigned)(t.ke - t.ks) * wpl) : 0u);
+  unsigned wst = stp ? wo : WL_OOB_LANE;
+  if (WIDE && WL_ABW_PAD) {   // every lane of a core row that is an interior row: lane lx -> slot (lx − 1) mod 32 of the tile's segment (the pair's own slot for the core lanes)
+    const int lx = threadIdx.x & (PT_X - 1), ly = (int)(threadIdx.x >> 6) + (int)((threadIdx.x >> 5) & 1u) * (PT_Y / 2);
+    const bool row = ly >= 2 && ly < PT_Y - 2 && t.j >= 1 && t.j <= g.ny - 2;
+    const unsigned seg = (unsigned)((t.i0 + 2 - 2 * lx) / wl::ABW_CX);
+    wst = row ? (unsigned)t.j * wl::abw_pitch(g.nx) + seg * wl::ABW_SEG + (unsigned)((lx + PT_X - 1) & (PT_X - 1)) * wl::ABW_ELT : WL_OOB_LANE;
+  }
 #ifdef WL_STAMP
   unsigned long long st_pre = 0, st_bar = 0, st_swp = 0, st_sto = 0, st_n = 0;
 #endif
@@ -281,7 +318,7 @@ __global__ void __launch_bounds__(PT_N, WL_A_WAVES) k_gsrb2_A(GridX g, float* __
       }
       const unsigned pk = (unsigned)K * sz4;                        // byte offset of plane K
       n_r0 = bld2(b_r, ob0, pk + sz4);                              // (lanes outside the array read the plane's corner ghost pair)
-      if (PRO) n_x0 = bld2(b_x, vst | ((K + 1 >= t.ks && K + 1 < t.ke && K + 1 >= pa.xk0 && K + 1 < pa.xk1) ? 0u : WL_OOB_STEP), pk + sz4);
+      if (PRO && !WIDE) n_x0 = bld2(b_x, vst | ((K + 1 >= t.ks && K + 1 < t.ke && K + 1 >= pa.xk0 && K + 1 < pa.xk1) ? 0u : WL_OOB_STEP), pk + sz4);
       if (PRO == 2) {
         const unsigned a = (KODD ? rc : ro) + (unsigned)(((K + 1) >> 1) + 1 + pa.zoff) * (unsigned)pa.gc.sz;   // K+1 odd: the other coarse row
         n_c = make_float2(pa.xc[a], pa.xc[a + 1]);
@@ -302,7 +339,7 @@ __global__ void __launch_bounds__(PT_N, WL_A_WAVES) k_gsrb2_A(GridX g, float* __
         s += (zm1 * c2 + zp1 * c2);
         r0.y = t.in1 ? r0.y - pa.w * s : r0.y;
         // (a pair on an x-wall holds one ghost cell: it is written back unchanged, so every store is a whole pair)
-        xs = make_float2(t.st0 ? x0.x + pa.w * v0 : x0.x, t.st1 ? x0.y + pa.w * v1 : x0.y);
+        if (!WIDE) xs = make_float2(t.st0 ? x0.x + pa.w * v0 : x0.x, t.st1 ? x0.y + pa.w * v1 : x0.y);
       }
       e0.x = r0.x * k.idm0; e0.y = r0.y * k.idm1;                   // ϵ = r·iD
 #ifdef WL_STAMP
@@ -328,12 +365,18 @@ __global__ void __launch_bounds__(PT_N, WL_A_WAVES) k_gsrb2_A(GridX g, float* __
       sB[cb][t.lq] = e1.x; sB[cb][t.lq + PL_H] = e1.y;
       WL_ST(T3);
       // all stores of the step, issued unconditionally (see mkbuf): the next step's first use of n_r0/n_x0/n_c waits with a counted vmcnt
+      if (WIDE) {
+        const bool own2 = (K - 2) >= t.ks && (K - 2) < t.ke;
+        const float4 v = (!WL_ABW_PAD || stp) ? make_float4(r2.x, r2.y, e2.x, e2.y) : make_float4(0.f, 0.f, 0.f, 0.f);
+        bst4(b_w, wst | (own2 ? 0u : WL_OOB_STEP), own2 ? (unsigned)(K - 2 - t.ks) * wpl : 0u, v);
+      } else {
       if (PRO) {
         const bool own = K >= t.ks && K < t.ke;
         bst2(b_rn, vst | (own ? 0u : WL_OOB_STEP), pk, r0);
         bst2(b_xs, vst | ((own && K >= pa.xk0 && K < pa.xk1) ? 0u : WL_OOB_STEP), pk, xs);
       }
       bst2(b_em, vst | (((K - 2) >= t.ks && (K - 2) < t.ke) ? 0u : WL_OOB_STEP), pk - 2u * sz4, e2);
+      }
 #ifdef WL_STAMP
       { WL_ST(T4); st_pre += T1 - T0; st_bar += T2 - T1; st_swp += T3 - T2; st_sto += T4 - T3; st_n++; }
 #endif
@@ -391,7 +434,7 @@ __global__ void __launch_bounds__(PT_N, WL_A_WAVES) k_gsrb2_A(GridX g, float* __
       s += (ym1 * k.ky + yp1 * k.kyp);
       s += (zm1 * lz0 + zp1 * lzp0);
       if (t.in1) r0.y = r0.y - pa.w * s;
-      xs = make_float2(x0.x + pa.w * v0, x0.y + pa.w * v1);
+      if (!WIDE) xs = make_float2(x0.x + pa.w * v0, x0.y + pa.w * v1);
     }
     {   // ϵ = r·iD   :142   (ghost cells and planes: iD = 0)
       const bool edge = (lz0 == 0.f) || (lzp0 == 0.f);
@@ -420,6 +463,9 @@ __global__ void __launch_bounds__(PT_N, WL_A_WAVES) k_gsrb2_A(GridX g, float* __
     sB[cb][t.lq] = e1.x; sB[cb][t.lq + PL_H] = e1.y;
     // ---- all stores of the step, behind the wait for the prefetched plane (see WL_SETTLE)
     if (PRO == 2) WL_SETTLE3(n_r0, n_x0, n_c); else if (PRO) WL_SETTLE2(n_r0, n_x0); else WL_SETTLE2(n_r0, n_r0);
+    if (WIDE) {   // (the planes [ks,ke) are interior planes: what the dense form stores of r′ at step K−2 and of ϵ_mid at step K, the pair written whole)
+      if (stp && (K - 2) >= t.ks && (K - 2) < t.ke) stw(emid, (size_t)(K - 2) * wpl + wo, make_float4(r2.x, r2.y, e2.x, e2.y));
+    } else
     if (t.st0 || t.st1) {
       if (PRO && plK && K >= t.ks && K < t.ke) {
         st2(pa.rnew, o0, r0, t.st0, t.st1);
@@ -436,7 +482,9 @@ __global__ void __launch_bounds__(PT_N, WL_A_WAVES) k_gsrb2_A(GridX g, float* __
 // norms; the launch leaves ϵ_mid and r untouched, so B_RONLY can produce rout later).  B_RONLY: sweeps 3 and 4 and r' as ever, rout stored; x and x_c are
 // neither loaded nor stored, no norms.  The statements that produce r' and x are the same in every mode.
 // ------------------------------------------------------------------------------------------------------------------
-template <int NORMS, int EPS, int OUT = wl::B_BOTH>
+// WIDE: `emid` is the level's exchange buffer W and `r` is not read: one 16-byte load per step brings ϵ_mid of plane K+1 and r′ of plane K+1 — r′ one plane
+// earlier than the dense form loads it, so it is carried one more step (r0).
+template <int NORMS, int EPS, int OUT = wl::B_BOTH, int WIDE = 0>
 __global__ void __launch_bounds__(PT_N, WL_B_WAVES) k_gsrb2_B(GridX g, float* __restrict__ eout, float* __restrict__ rout, float* __restrict__ x, const float* __restrict__ emid,
                                                      const float* __restrict__ r, float w, int zchunk, double* __restrict__ part, float* __restrict__ pmax, wl::ConstL cl, XPro xp) {
   __shared__ float sA[2][PL_SZ];   // ϵ_mid of the newest plane
@@ -450,14 +498,22 @@ __global__ void __launch_bounds__(PT_N, WL_B_WAVES) k_gsrb2_B(GridX g, float* __
   const int jpar = (t.j + g.gk) & 1;
   const int oth0 = PL_H + t.lq - 1, oth1 = t.lq + 1;
   float2 e0 = {0.f, 0.f}, e1 = e0, e2 = e0, e3 = e0, e4 = e0, r1 = e0, r2 = e0, r3 = e0, n_e0, n_r1, n_x3 = e0, n_v3 = e0;
+  float2 r0 = e0;                  // WIDE: r′ of plane K (n_r1 then holds r′ of the plane n_e0 is of)
+  const unsigned wpl = WIDE ? (unsigned)g.ny * wl::abw_pitch(g.nx) : 0u;                                            // bytes per plane of W
+  const unsigned wo = (WIDE && t.indom) ? (unsigned)t.j * wl::abw_pitch(g.nx) + wl::abw_slot(t.i0) : 0u;            // the pair inside a plane (lanes outside the array: the corner ghost pair, zeros)
   double nsum = 0.0; float nmax = 0.f;
   const int Kbeg = t.ks - 3, Kend = t.ke + 2;
   const bool stp = t.st0 || t.st1;
   const unsigned qxc = (xp.on && t.indom) ? (unsigned)dwn(t.i0, xp.cx) + (unsigned)dwn(t.j, xp.cy) * xp.csy : 0u;   // the pair's coarse parents: xc[qxc], xc[qxc+1] (+ plane)
   auto fetch = [&](int K) {
     const unsigned o0 = t.oc + (unsigned)K * (unsigned)g.sz;
+    if (WIDE) {   // (ghost planes of W hold zeros: the r′ of a plane that is not interior)
+      const float4 v = (t.indom && K >= 0 && K <= g.nz - 1) ? ldw(emid, (size_t)K * wpl + wo) : make_float4(0.f, 0.f, 0.f, 0.f);
+      n_r1 = make_float2(v.x, v.y); n_e0 = make_float2(v.z, v.w);
+    } else {
     n_e0 = (t.indom && K >= 0 && K <= g.nz - 1) ? ld2(emid, o0) : make_float2(0.f, 0.f);
     n_r1 = (t.indom && pint(g, K - 1)) ? ld2(r, o0 - (unsigned)g.sz) : make_float2(0.f, 0.f);
+    }
     if (OUT != wl::B_RONLY) {
     n_x3 = (stp && (K - 3) >= t.ks && (K - 3) < t.ke) ? ld2(x, o0 - 3u * (unsigned)g.sz) : make_float2(0.f, 0.f);
     if (xp.on && stp && (K - 3) >= t.ks && (K - 3) < t.ke) n_v3 = ld2u(xp.xc, qxc + (unsigned)(dwn(g.gk + K - 3, xp.cz) - xp.cgk) * xp.csz);
@@ -485,6 +541,9 @@ __global__ void __launch_bounds__(PT_N, WL_B_WAVES) k_gsrb2_B(GridX g, float* __
   const __amdgpu_buffer_rsrc_t b_em = mkbuf(emid, WL_LDBYTES(fbytes)), b_r = mkbuf(r, WL_LDBYTES(fbytes)), b_x = mkbuf(x, WL_LDBYTES(fbytes)), b_xs = mkbuf(x, WL_STBYTES(fbytes)), b_ro = mkbuf(rout, WL_STBYTES(fbytes)), b_xc = mkbuf(xp.xc, xp.cbytes);
   const unsigned vst = stp ? ob0 : WL_OOB_LANE;                    // store offset of the lane (tile core ∧ interior), else out of range
   const unsigned vxc = stp ? qxc * 4u : WL_OOB_LANE;               // the pair's coarse parents
+  // WIDE: the chunk's descriptor over the planes this workgroup reads, [max(Kbeg,0), min(Kend,nz−1)]; every lane's load is in range
+  const int wp0 = Kbeg > 0 ? Kbeg : 0, wp1 = Kend < g.nz - 1 ? Kend : g.nz - 1;
+  const __amdgpu_buffer_rsrc_t b_w = mkbufw(emid, WIDE ? (size_t)wp0 * wpl : 0, WIDE ? WL_LDBYTES((unsigned)(wp1 - wp0 + 1) * wpl) : 0u);
   auto fast = [&](auto jodd_c) {
     constexpr bool JODD = decltype(jodd_c)::value;
     auto step = [&](auto kodd_c, const int K) {
@@ -492,11 +551,17 @@ __global__ void __launch_bounds__(PT_N, WL_B_WAVES) k_gsrb2_B(GridX g, float* __
       constexpr bool ACT1 = JODD != KODD;                           // the cell of the pair that this colour sweep updates
       constexpr int pb = KODD ? 0 : 1, cb = KODD ? 1 : 0;
       e4 = e3; e3 = e2; e2 = e1; e1 = e0; r3 = r2; r2 = r1;
-      e0 = n_e0; r1 = n_r1;
+      e0 = n_e0;
+      if (WIDE) { r1 = r0; r0 = n_r1; } else r1 = n_r1;
       const float2 x3 = xp.on ? make_float2(n_x3.x + xp.w * n_v3.x, n_x3.y + xp.w * n_v3.y) : n_x3;
       const unsigned pk = (unsigned)K * sz4;                        // byte offset of plane K
+      if (WIDE) {
+        const float4 v = bld4(b_w, wo, (unsigned)(K + 1 - wp0) * wpl);
+        n_r1 = make_float2(v.x, v.y); n_e0 = make_float2(v.z, v.w);
+      } else {
       n_e0 = bld2(b_em, ob0, pk + sz4);                             // (lanes outside the array read the plane's corner ghost pair)
       n_r1 = bld2(b_r, ob0, pk);
+      }
       if (OUT != wl::B_RONLY) {
         const unsigned mo = ((K - 2) >= t.ks && (K - 2) < t.ke) ? 0u : WL_OOB_STEP;
         n_x3 = bld2(b_x, vst | mo, pk - 2u * sz4);
@@ -558,7 +623,8 @@ __global__ void __launch_bounds__(PT_N, WL_B_WAVES) k_gsrb2_B(GridX g, float* __
       if (K > Kend) break;
     }
     e4 = e3; e3 = e2; e2 = e1; e1 = e0; r3 = r2; r2 = r1;
-    e0 = n_e0; r1 = n_r1;
+    e0 = n_e0;
+    if (WIDE) { r1 = r0; r0 = n_r1; } else r1 = n_r1;
     const float2 x3 = xp.on ? make_float2(n_x3.x + xp.w * n_v3.x, n_x3.y + xp.w * n_v3.y) : n_x3;
     if (K < Kend) fetch(K + 1);
     const float lz0 = cf(g.gk + K + 1, g.gnz, c2), lz1 = cf(g.gk + K, g.gnz, c2), lz2 = cf(g.gk + K - 1, g.gnz, c2), lz3 = cf(g.gk + K - 2, g.gnz, c2);
@@ -672,7 +738,7 @@ int gsrb_pair_A(float* emid, const float* r, const GridX& g, const wl::ConstL& c
   WL_LAUNCH_CHECK(); return 0;
 }
 int gsrb_pair_A_pro(float* emid, float* rnew, float* x, const float* r, const float* xc, const GridX& g, const GridX& gc, float w, const wl::ConstL& cl, hipStream_t s,
-                    int xk0 = -(1 << 30), int xk1 = 1 << 30) {
+                    int xk0 = -(1 << 30), int xk1 = 1 << 30, float* wide = nullptr) {
   const int zc = zchunk2(g, 2, 2);
   const int nt = ptile_count(g.nx, g.ny, 2, 2), per = (nt + 7) >> 3, nch = (g.k1 - g.k0 + zc - 1) / zc;
   ProArgs2 pa{xc, x, rnew, gc, gc.nx < g.nx, gc.ny < g.ny, gc.gnz < g.gnz, w, xk0, xk1, 0};
@@ -680,12 +746,18 @@ int gsrb_pair_A_pro(float* emid, float* rnew, float* x, const float* r, const fl
   // even g.gk its parity is K's and its coarse parent is the local coarse plane ((K+1)>>1) + g.gk/2 − gc.gk (gc may be a slab or a replicated level).
   const bool fullc = pa.cx && pa.cy && pa.cz && (g.gk & 1) == 0 && 2 * (gc.nx - 2) == g.nx - 2 && 2 * (gc.ny - 2) == g.ny - 2 && 2 * (gc.gnz - 2) == g.gnz - 2;
   if (fullc) pa.zoff = g.gk / 2 - gc.gk;
+  if (wide) {   // r′ and ϵ_mid to the exchange buffer; x is kernel B's
+    if (xk0 < xk1) { wl_set_error("gsrb_pair_A_pro: the wide exchange needs the x increment deferred to kernel B"); return WL_EINVAL; }
+    if (fullc && g_pro_fast) hipLaunchKernelGGL((k_gsrb2_A<2, 1>), dim3((unsigned)(8 * per * nch)), dim3(PT_N), 0, s, g, wide, r, zc, pa, cl);
+    else hipLaunchKernelGGL((k_gsrb2_A<1, 1>), dim3((unsigned)(8 * per * nch)), dim3(PT_N), 0, s, g, wide, r, zc, pa, cl);
+    WL_LAUNCH_CHECK(); return 0;
+  }
   if (fullc && g_pro_fast) hipLaunchKernelGGL((k_gsrb2_A<2>), dim3((unsigned)(8 * per * nch)), dim3(PT_N), 0, s, g, emid, r, zc, pa, cl);
   else hipLaunchKernelGGL((k_gsrb2_A<1>), dim3((unsigned)(8 * per * nch)), dim3(PT_N), 0, s, g, emid, r, zc, pa, cl);
   WL_LAUNCH_CHECK(); return 0;
 }
 int gsrb_pair_B(float* eps, float* rout, float* x, const float* emid, const float* r, const GridX& g, float w,
-                const RedWs* ws, int slot_d, int slot_f, const wl::ConstL& cl, hipStream_t s, const wl::XDefer* xd, int out) {
+                const RedWs* ws, int slot_d, int slot_f, const wl::ConstL& cl, hipStream_t s, const wl::XDefer* xd, int out, const float* wide) {
   XPro xp{};
   if (out == wl::B_RONLY) { ws = nullptr; xd = nullptr; eps = nullptr; }   // the recompute of a skipped rout: no x, no norms, no ϵ
   if (xd) xp = XPro{xd->xc, 1, xd->w, xd->gc.nx < g.nx, xd->gc.ny < g.ny, xd->gc.gnz < g.gnz, (unsigned)xd->gc.sy, (unsigned)xd->gc.sz, xd->gc.gk, (unsigned)(xd->gc.cs * 4)};
@@ -696,6 +768,13 @@ int gsrb_pair_B(float* eps, float* rout, float* x, const float* emid, const floa
   double* pa = norms ? ws->pa : nullptr; float* pm = norms ? ws->pm : nullptr;
 #define WL_GB(NF, EF) hipLaunchKernelGGL((k_gsrb2_B<NF, EF>), dim3(nb), dim3(PT_N), 0, s, g, eps, rout, x, emid, r, w, zc, pa, pm, cl, xp)
 #define WL_GBO(NF, OF) hipLaunchKernelGGL((k_gsrb2_B<NF, 0, OF>), dim3(nb), dim3(PT_N), 0, s, g, eps, rout, x, emid, r, w, zc, pa, pm, cl, xp)
+#define WL_GBW(NF, OF) hipLaunchKernelGGL((k_gsrb2_B<NF, 0, OF, 1>), dim3(nb), dim3(PT_N), 0, s, g, eps, rout, x, wide, (const float*)nullptr, w, zc, pa, pm, cl, xp)
+  if (wide) {   // ϵ_mid and r′ from the exchange buffer kernel A's wide form filled
+    if (eps || (ws && !norms)) { wl_set_error("gsrb_pair_B: the wide exchange stores no ϵ and needs its norms from the kernel"); return WL_EINVAL; }
+    if (out == wl::B_XONLY) { if (norms) WL_GBW(1, wl::B_XONLY); else WL_GBW(0, wl::B_XONLY); }
+    else if (out == wl::B_RONLY) WL_GBW(0, wl::B_RONLY);
+    else { if (norms) WL_GBW(1, wl::B_BOTH); else WL_GBW(0, wl::B_BOTH); }
+  } else
   if (out == wl::B_XONLY) {
     // (the fallback norms below read the stored array: the caller asks gsrb_pair_B_kernel_norms first)
     if (eps || (ws && !norms)) { wl_set_error("gsrb_pair_B: the x-only form stores no ϵ and needs its norms from the kernel"); return WL_EINVAL; }
@@ -703,12 +782,15 @@ int gsrb_pair_B(float* eps, float* rout, float* x, const float* emid, const floa
   } else if (out == wl::B_RONLY) WL_GBO(0, wl::B_RONLY);
   else
   if (norms) { if (eps) WL_GB(1, 1); else WL_GB(1, 0); } else { if (eps) WL_GB(0, 1); else WL_GB(0, 0); }
+#undef WL_GBW
 #undef WL_GBO
 #undef WL_GB
   if (norms) WL_TRY(wl::finalize_sum_max(*ws, (int)nb, slot_d, slot_f, s));
   else if (ws) WL_TRY(wl::norms_dev(rout, g, *ws, slot_d, slot_f, s));
   WL_LAUNCH_CHECK(); return 0;
 }
+// the longest z-chunk of kernels A and B on this grid (the planes a workgroup's descriptor over W spans are at most this + 7)
+int wide_chunk_planes(const GridX& g) { const int a = zchunk2(g, 2, 2), b = zchunk2(g, 4, 3); return a > b ? a : b; }
 // the launch of gsrb_pair_B for this grid takes its norms from the kernel's registers (not from the stored rout)
 bool gsrb_pair_B_kernel_norms(const GridX& g) {
   const int zc = zchunk2(g, 4, 3);

@@ -66,12 +66,20 @@ int wl_mg::build(float* x, float* L, float* z, const wl_grid& g0, unsigned per, 
     if (l == 0) { v.x = x; v.L = L; v.z = z; }
     else { v.L = p; p += nc * (size_t)grids[l].D; v.x = p; p += nc; v.z = p; p += nc; }
   }
+  // the exchange buffers W of the levels that can run the pair kernels on a single domain (512-byte aligned by hipMalloc, zeroed once: its ghost rows and planes
+  // are never written).  A level whose allocation fails keeps the dense exchange.
+  if (!c && !per) for (Level& v : lv) {
+    const size_t wb = v.dist ? 0 : wl::gsrb_pair_wide_bytes(v.x_);
+    if (!wb) continue;
+    if (hipMalloc((void**)&v.wx, wb) != hipSuccess) { (void)hipGetLastError(); v.wx = nullptr; continue; }
+    WL_HIP(hipMemset(v.wx, 0, wb));
+  }
   hipStream_t s = 0;
   WL_TRY(update(s));                                                                       // restrictML :39 + Poisson ctor :36
   WL_HIP(hipStreamSynchronize(s));
   return 0;
 }
-wl_mg::~wl_mg() { if (slab) (void)hipFree(slab); if (red) (void)hipFree(red); if (side) (void)hipStreamDestroy(side); if (ev_decided) (void)hipEventDestroy(ev_decided); }
+wl_mg::~wl_mg() { for (Level& v : lv) if (v.wx) (void)hipFree(v.wx); if (slab) (void)hipFree(slab); if (red) (void)hipFree(red); if (side) (void)hipStreamDestroy(side); if (ev_decided) (void)hipEventDestroy(ev_decided); }
 
 // coarse face coefficients of level l from level l-1 (restrictL! :42-48), slab aware
 static int restrictL_level(wl_mg& m, size_t l, hipStream_t s) {
@@ -140,7 +148,7 @@ int wl_mg::settle_r(hipStream_t s) {
   r_stale = false; n_rskip_redo++;
   // the pair kernel itself, with the coefficients of the launch that skipped the store — not gsrb_fused_B's choice of today: the process-wide "pair" switch or
   // "constl" (update!) may have withdrawn the pair kernels since, and only they store r' alone
-  return wl::gsrb_pair_B(nullptr, p.r, p.x, p.em, p.rs, p.x_, r_stale_w, nullptr, WL_RD_L1, WL_RF_LINF, r_stale_cl, s, nullptr, wl::B_RONLY);
+  return wl::gsrb_pair_B(nullptr, p.r, p.x, p.em, p.rs, p.x_, r_stale_w, nullptr, WL_RD_L1, WL_RF_LINF, r_stale_cl, s, nullptr, wl::B_RONLY, r_stale_wide ? p.wx : nullptr);
 }
 // … for a reader that names no stream: behind the launch that skipped the store, on its stream (stream 0 if that stream is gone), and complete on return —
 // whichever stream the caller then reads r on finds it current
@@ -168,6 +176,8 @@ wl_mg::SmoothPlan wl_mg::plan_smooth(const Level& p, int it, bool want_norms, in
   q.form = zsplit_ranges(p).on ? Smooth::ZSplit : !(q.pro && deep_slab(p)) ? Smooth::Blocked : (overlap_smooth && p.x_.k1 - p.x_.k0 >= 16) ? Smooth::DeepSlabOverlap : Smooth::DeepSlab;
   q.xdefer = q.pro && use_xdefer && wl::gsrb_pair_B_ok(store_eps ? p.eps : nullptr, p.r, p.x, p.em, p.rs, p.x_, p.cl);
   if (q.pro && q.form == Smooth::Blocked && b_xonly_ok(p, bout, want_norms)) q.bout = wl::B_XONLY;   // skip_r: r' stays in kernel B's registers (the norms) — p.em and p.rs are left as they are, so settle_r can still produce it
+  // the wide exchange: only the one-launch form on a single domain, with x left to kernel B (kernel A's wide form has no x stage) and the norms, if any, from kernel B
+  q.wide = q.form == Smooth::Blocked && q.pro && q.xdefer && use_wide && !store_eps && p.wx && !p.dist && !comm && !perdir && (!want_norms || wl::gsrb_pair_B_kernel_norms(p.x_));
   return q;
 }
 int wl_mg::smooth(int l, int it, float w, hipStream_t s, bool want_norms, bool* norms_done, int bout) {
@@ -190,15 +200,16 @@ int wl_mg::smooth(int l, int it, float w, hipStream_t s, bool want_norms, bool* 
   if (plan.form == Smooth::ZSplit && want_norms) { ZPart parts[3]; zsplit_parts(*this, p, parts); for (int i = 0; i < 3; i++) if (parts[i].any()) norm_slots |= 1 << i; }
   if (norms_done) *norms_done = want_norms;
   if (l == 0 && plan.pro) last_xdefer = plan.xdefer ? 1 : 0;
-  if (l == 0 && plan.bout == wl::B_XONLY) { r_stale = true; r_stale_w = w; r_stale_stream = s; r_stale_cl = p.cl; n_rskip++; }
+  if (l == 0 && plan.bout == wl::B_XONLY) { r_stale = true; r_stale_w = w; r_stale_stream = s; r_stale_cl = p.cl; r_stale_wide = plan.wide; n_rskip++; }
+  if (l == 0 && plan.wide) n_wide++;
   return 0;
 }
 // kernel B of the level, or of the plane range g of it.  coarse (a prolongation was absorbed): kernel A's extra stage left r' in p.rs and B stores the final
 // residual to p.r — and applies `x += ω·x_c↓` too where A handed it on (xdef); else B goes from p.r to p.rs
-static int launch_B(wl_mg& m, wl_mg::Level& p, const GridX& g, const wl_mg::Level* coarse, bool xdef, float w, const RedWs* nws, WlNormSlots sl, const wl::ConstL& cl, hipStream_t s, int out = wl::B_BOTH) {
+static int launch_B(wl_mg& m, wl_mg::Level& p, const GridX& g, const wl_mg::Level* coarse, bool xdef, float w, const RedWs* nws, WlNormSlots sl, const wl::ConstL& cl, hipStream_t s, int out = wl::B_BOTH, const float* wide = nullptr) {
   const bool pro = coarse != nullptr;
   const wl::XDefer xd{pro ? coarse->x : nullptr, pro ? coarse->x_ : g, w};
-  return wl::gsrb_fused_B(m.store_eps ? p.eps : nullptr, pro ? p.r : p.rs, p.x, p.em, pro ? p.rs : p.r, p.L, g, w, nws, sl.d, sl.f, cl, s, pro && xdef ? &xd : nullptr, out);
+  return wl::gsrb_fused_B(m.store_eps ? p.eps : nullptr, pro ? p.r : p.rs, p.x, p.em, pro ? p.rs : p.r, p.L, g, w, nws, sl.d, sl.f, cl, s, pro && xdef ? &xd : nullptr, out, wide);
 }
 // z-slab: what kernel B reads across the slab faces — ϵ_mid (3 planes) and, behind a prolongation stage, r' (2 planes) in one RCCL group: one exchange latency instead of two
 int wl_mg::exchange_for_B(Level& p, bool with_rs, hipStream_t s) {
@@ -217,12 +228,12 @@ int wl_mg::smooth_blocked(Level& p, Level* coarse, int l, float w, const SmoothP
   WL_TRY(halo(p, p.r, 1, s, 2));
   {
     ProfScope pa(l == 0 ? WL_PROF_GS_A : -1, s);
-    if (coarse) WL_TRY(wl::gsrb_fused_A_pro(p.em, p.rs, p.x, p.r, coarse->x, p.L, p.x_, coarse->x_, w, p.cl, s, -(1 << 30), 1 << 30, &xdef));
+    if (coarse) WL_TRY(wl::gsrb_fused_A_pro(p.em, p.rs, p.x, p.r, coarse->x, p.L, p.x_, coarse->x_, w, p.cl, s, -(1 << 30), 1 << 30, &xdef, false, plan.wide ? p.wx : nullptr));
     else WL_TRY(wl::gsrb_fused_A(p.em, p.r, p.L, p.x_, p.cl, s));
   }
   WL_TRY(exchange_for_B(p, coarse != nullptr, s));
   ProfScope pb(l == 0 ? WL_PROF_GS_B : -1, s);
-  return launch_B(*this, p, p.x_, coarse, xdef, w, plan.want_norms ? &ws : nullptr, WL_ZS_NORMS[0], p.cl, s, plan.bout);
+  return launch_B(*this, p, p.x_, coarse, xdef, w, plan.want_norms ? &ws : nullptr, WL_ZS_NORMS[0], p.cl, s, plan.bout, plan.wide ? p.wx : nullptr);
 }
 // z-slab, ONE exchange round per smooth!: r travels 5 planes deep and kernel A also computes r' and ϵ_mid on the 3 (2) ghost planes kernel B reads, instead of
 // receiving them (x is updated on the owned planes only).  5 planes instead of 2+3+2, one latency instead of two, ≈6 redundant planes of kernel A per rank.

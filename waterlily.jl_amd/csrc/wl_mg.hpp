@@ -16,6 +16,7 @@ struct wl_mg {
     wl_grid g; GridX x_;
     float *L = nullptr, *D = nullptr, *iD = nullptr, *x = nullptr, *eps = nullptr, *r = nullptr, *z = nullptr;
     float *em = nullptr, *rs = nullptr;   // scratch of the fused smoother: ϵ after sweep 2, new residual (ghosts stay zero)
+    float* wx = nullptr;                  // exchange buffer W (wl_abwide.hpp): both of them as one float4 per pair, for the smooth! that plan_smooth calls wide; null: the level has none
     wl::ConstL cl{};                 // constant-coefficient level (verified at update!)
     bool xzero = false;              // x ≡ 0 is implied (the V-cycle's fill!(x,0) was skipped): the next Jacobi! writes x instead of updating it
     // body levels: the coefficients deviate from the constant pattern only on planes [za,zb]; smooth! runs the pair kernels on the other planes
@@ -43,10 +44,12 @@ struct wl_mg {
   bool skip_r = false;
   int rskip_slot = -1;
   int rskip_hist[2] = {0, 0};      // iterations of the last solve that stood, per slot (0: none yet — store)
+  bool r_stale_wide = false;                        // … and where that launch read ϵ_mid and r′: the level's exchange buffer W (the late store reads the same)
   bool r_stale = false; float r_stale_w = 0.f;      // lv[0].r was not written by the last smooth!(0): kernel B's inputs lv[0].em, lv[0].rs are intact, ω as given
   hipStream_t r_stale_stream = nullptr;             // … and the stream that launch ran on: where a stream-less reader (wl_mg_level_field) has r produced, and waits for it
   wl::ConstL r_stale_cl{};                          // … and the coefficients it ran with: the late store is that pair kernel again, whatever "pair" or "constl" have been set to since
   long n_rskip = 0, n_rskip_redo = 0;      // finest-level launches that skipped the store / r-only launches (lazy ones included)
+  long n_wide = 0;                         // finest-level smooth! calls that went through the exchange buffer W
   int settle_r(hipStream_t s);
   int settle_r_for_reader();
   bool use_fused = true;    // temporally blocked GaussSeidelRB! on eligible levels (wl_fused.hip)
@@ -76,6 +79,7 @@ struct wl_mg {
   int x_halo_depth = 1;     // z-slabs: ghost planes of x refreshed at the end of solver! (the projection tail reads 1; the fused projection head of the NEXT solve reads 2)
   int last_xdefer = -1;     // what the finest level's last smooth! with a pending prolongation decided: 1 = x += ω·x_c↓ deferred to kernel B, 0 = applied by kernel A (−1: none yet)
   bool use_xdefer = true;   // pair smoother: the V-cycle's `x += ω·x_c↓` is applied by kernel B together with its own increment (wl::XDefer)
+  bool use_wide = true;     // … and kernel A then hands r′ and ϵ_mid to kernel B through the level's exchange buffer W, where plan_smooth finds the launch eligible
   bool overlap_smooth = true;   // z-slabs: the one deep r exchange of a smooth! overlaps kernel A's interior planes (boundary slices after the wait)
   bool use_tail = true;     // levels of <= WL_TAIL_CELLS cells: the rest of the V-cycle in one launch (k_vcycle_tail)
   bool tail_ok(int first) const;
@@ -121,6 +125,7 @@ struct wl_mg {
     bool xdefer;                // … and its `x += ω·x_c↓` is handed on to kernel B (wl::XDefer); ZSplit decides per range and reports the last range's
     int bout;                   // wl::BOut of kernel B
     bool want_norms;
+    bool wide = false;          // Blocked with pro and xdefer, no store_eps, on a level that has W: r′ and ϵ_mid travel through W; every other launch uses p.rs and p.em
   };
   SmoothPlan plan_smooth(const Level& p, int it, bool want_norms, int bout) const;
   int smooth_passes(Level& p, int l, int it, float w, hipStream_t s);

@@ -1025,7 +1025,7 @@ int wl_sim_set_option(wl_sim* s, const char* name, int value) {
   if (n == "constl") { s->mg->use_constl = value != 0; return s->mg->update(0); }
   if (n == "tail") { s->mg->use_tail = value != 0; return 0; }
   if (n == "tail_lds") { wl::tail_lds_enable(value); return 0; }
-  if (n == "xdefer") { s->mg->use_xdefer = value != 0; return 0; }
+  if (n == "xdefer") { s->mg->use_xdefer = value != 0; s->mg->use_wide = value == 1; return 0; }   // 1: … and kernel A hands r′ and ϵ_mid to kernel B through the level's exchange buffer where eligible; 2: deferred x with the two dense arrays
   if (n == "overlap_smooth") { s->mg->overlap_smooth = value != 0; return 0; }
   if (n == "body_tile") { wl::conv_body_tile_enable(value); return 0; }
   if (n == "skip_fill") { s->mg->skip_fill = value != 0; return 0; }
@@ -1088,6 +1088,7 @@ int wl_sim_counter(wl_sim* s, const char* name, long* out) {
   if (n == "tailspec") { *out = s->n_tailspec; return 0; }
   if (n == "tailspec_armed") { *out = s->n_tailspec_armed; return 0; }
   if (n == "xdefer") { *out = s->mg->last_xdefer; return 0; }
+  if (n == "abwide") { *out = s->mg->n_wide; return 0; }                          // finest-level smooth! calls whose r′ and ϵ_mid went through the exchange buffer W
   // which body-aware path ran, and what the masks held at the last refresh (measure!/update!)
   if (n == "hybrid") { *out = s->n_hybrid; return 0; }
   if (n == "body_tile") { *out = wl::conv_body_tile_launches(); return 0; }      // (process-wide, like the switch: read it as a difference)
