@@ -86,6 +86,88 @@ def test_one_leaf_program_equals_wl_measure_body(w, body):
     assert w.lib().wl_launch_count() > n0
 
 
+# ---- the closed-form wl_body entry points against what they computed before they became one-leaf programs (tests/golden/make_body_parent.py) ----
+_X0_PARENT = (7.3, 8.7, 6.1)
+
+
+@pytest.fixture(scope="module")
+def parent():
+    import json
+    import os
+    raw = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "body_parent.npz"))
+    raw = {k: raw[k] for k in raw.files}
+    # (an array that repeats an earlier one bit for bit is stored as "=<that key>": make_body_parent.py pack)
+    z = {k: (raw[str(v)[1:]] if v.dtype.kind == "U" and str(v).startswith("=") else v) for k, v in raw.items()}
+    return z, json.loads(str(z["cases"]))
+
+
+def _int_field(shape, c):
+    """((7i + 13j + 29k + 5c) mod 17 − 8) / 4 on the 0-based array indices: exact in float32"""
+    idx = np.indices(shape)
+    s = 5 * c + sum(wt * ix for wt, ix in zip((7, 13, 29), idx))
+    return ((s % 17 - 8) / 4).astype(np.float32)
+
+
+def _body_tuple(spec):
+    return tuple(tuple(v) if isinstance(v, list) else v for v in spec)
+
+
+def _as_leaf(w, body):
+    """the same closed-form body as a one-leaf program; a translation velocity becomes the θ = 0 map's V"""
+    from waterlily_jl_amd import bodies
+    still = _strip_velocity(body)
+    if len(body) == len(still):
+        return bodies.Body(still)
+    D = len(body[1])
+    return bodies.Body(still, bodies.RigidMap((0.0,) * D, 0.0 if D == 2 else (0.0, 0.0, 0.0), V=body[-1]))
+
+
+@pytest.mark.parametrize("case", range(7))
+def test_wl_body_entry_points_equal_the_parent_commit(w, parent, case):
+    """σ, μ₀, μ₁, V of wl_measure_body and the four Float64 read-outs, bit for bit what the commit recorded in the fixture computed with its own
+    k_measure_body / k_pforce_body / k_vforce_body — through wl_*_body and through the one-leaf wl_*_bodyset calls"""
+    z, cases = parent
+    name, N, spec, eps = cases[case]
+    D, body = len(N), _body_tuple(spec)
+    moving = len(body) != len(_strip_velocity(body))
+    x0 = _X0_PARENT[:D]
+    still = _strip_velocity(body)
+    for measured, read in ((body, still), (_as_leaf(w, body), _as_leaf(w, still))):
+        f = w.Flow(tuple(N), (1.0,) + (0.0,) * (D - 1), nu=0.02)
+        _poison(w, f)
+        w.measure_(f, measured, eps)
+        got = _fields(w, f)
+        for k in got:
+            assert np.array_equal(got[k], z[f"{name}/{k}"]), (name, k)
+        f.p.copy_(w.to_device(_int_field(tuple(f.p.shape), 0)))
+        f.u.copy_(w.to_device(np.stack([_int_field(tuple(f.p.shape), c + 1) for c in range(D)], -1)))
+        assert np.array_equal(w.pressure_force(f, read), z[f"{name}/pforce"]), name
+        assert np.array_equal(w.viscous_force(f, read), z[f"{name}/vforce"]), name
+        assert np.array_equal(w.pressure_moment(x0, f, read), z[f"{name}/pmoment"]), name
+        assert np.array_equal(w.viscous_moment(x0, f, read), z[f"{name}/vmoment"]), name
+    assert z[f"{name}/pforce"].any() and (np.abs(z[f"{name}/V"]).max() == 0.25) == moving
+
+
+def test_sim_measure_body_leaves_the_arrays_of_wl_measure_body(w, parent):
+    """wl_sim_measure_body on a has_body handle against wl_measure_body on a Flow (the fixture's translating sphere); the force recorder follows the body"""
+    z, cases = parent
+    name, N, spec, eps = cases[4]
+    body = _body_tuple(spec)
+    sf = w.FusedSimulation(tuple(N), (1.0, 0.0, 0.0), 8, nu=0.02, has_body=True)
+    sf.set_force_record(w.Body(("sphere", (4.0, 4.0, 4.0), 2.0)), x0=_X0_PARENT, capacity=4)
+    t0 = sf.counter("force_tiles")
+    sf.measure_body_(body, eps)
+    f = w.Flow(tuple(N), (1.0, 0.0, 0.0), nu=0.02)
+    w.measure_(f, body, eps)
+    ref = _fields(w, f)
+    for k in ("sigma", "mu0", "mu1", "V"):
+        assert np.array_equal(sf.field(k), ref[k]), k
+        assert np.array_equal(ref[k], z[f"{name}/{k}"]), k
+    sg = w.FusedSimulation(tuple(N), (1.0, 0.0, 0.0), 8, nu=0.02, has_body=True)
+    sg.set_force_record(w.Body(_strip_velocity(body)), x0=_X0_PARENT, capacity=4)
+    assert sf.counter("force_tiles") == sg.counter("force_tiles") > t0 > 0
+
+
 def _approx(a, b):
     """Julia's ≈ with the default rtol = √eps(Float32), norm-based on vectors"""
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)

@@ -1,4 +1,4 @@
-// Closed-form body helpers shared by the measure!/force kernels of wl_sim.hip and wl_bodyset.hip (device code, gfx950).
+// Closed-form body helpers of the measure!/force kernels (wl_bodyset.hip, wl_forces.hip; device code, gfx950) and the host side of a body program.
 #pragma once
 #include "wl_common.hpp"
 
@@ -11,8 +11,8 @@ __device__ __forceinline__ float eps_at(float d) { d = fabsf(d); return d == 0.f
 __device__ __forceinline__ float mu0_(float d, float e) { return d / e < -1 + sqrtf(eps_at(d)) ? 0.f : kern0_(fminf(d / e, 1.f)); }
 __device__ __forceinline__ float mu1_(float d, float e) { return e * kern1_(fminf(fmaxf(d / e, -1.f), 1.f)); }
 // Closed-form AutoBody (src/AutoBody.jl:21,29-37): kind 1 sdf = |m∘(x−c)|−R (sphere/circle; an axis with m=0 is dropped: cylinder
-// along it), kind 2 sdf = m·(x−c) (plane, m need not be unit).  The map x−V·t is folded into c by the caller, V is the body velocity.
-struct BodyArg { int kind; float c[3], R, m[3], V[3]; };
+// along it), kind 2 sdf = m·(x−c) (plane, m need not be unit).  The map x−V·t is folded into c by the caller.
+struct BodyArg { int kind; float c[3], R, m[3]; };
 template <int D>
 __device__ __forceinline__ float body_sdf(const BodyArg& b, const float* x) {
   float s = 0.f;
@@ -20,7 +20,7 @@ __device__ __forceinline__ float body_sdf(const BodyArg& b, const float* x) {
   for (int q = 0; q < D; q++) { const float dx = b.m[q] * (x[q] - b.c[q]); s += dx * dx; }
   return sqrtf(s) - b.R;
 }
-// measure(body,x;fastd²): returns true when n was evaluated (then V = the body velocity), false on the early exits (n = V = 0)
+// measure(body,x;fastd²): returns true when n was evaluated (then V = the body's velocity), false on the early exits (n = V = 0)
 template <int D>
 __device__ __forceinline__ bool body_measure(const BodyArg& b, const float* x, float fastd2, float& d, float* n) {
   float rr = 0.f;
@@ -48,17 +48,20 @@ struct MomArg { int on; float x0[3]; };      // on: moments about x0 (pressure_m
 // A validated wl_bodyset as the kernels take it (by value, kernarg memory): components beyond D zeroed, capsule axes normalised; depth = the deepest the stack gets
 struct SetArg { int32_t n; int32_t leaf_root; int32_t depth; wl_body_node node[WL_BODYSET_MAX]; };
 namespace {
-__device__ __forceinline__ BodyArg body_arg(const wl_body_node& b) {
+__host__ __device__ __forceinline__ BodyArg body_arg(const wl_body_node& b) {
   BodyArg a; a.kind = b.kind; a.R = b.R;
-  for (int q = 0; q < 3; q++) { a.c[q] = b.c[q]; a.m[q] = b.m[q]; a.V[q] = 0.f; }
+  for (int q = 0; q < 3; q++) { a.c[q] = b.c[q]; a.m[q] = b.m[q]; }
   return a;
 }
 }  // namespace
 struct wl_comm;
 namespace wl {
 int bodyset_prepare(int D, const wl_bodyset* s, SetArg* out);      // WL_EINVAL (and the reason) for a malformed program
+// The only way a wl_body reaches a kernel: the program of one unmapped leaf.  The body's translation velocity travels in node[0].map.V (a leaf's measure returns
+// it where n was evaluated); bodyset_prepare keeps map zero for unmapped leaves, so there V = 0 as wlhip.h promises.  WL_EINVAL for a bad kind or a zero m.
+int bodyset_from_body(int D, const wl_body* b, SetArg* out);
 int bodyset_measure_fields(float* sigma, float* mu0, float* mu1, float* V, const GridX& G, const SetArg& P, float eps, int exitBC, unsigned perdir, hipStream_t q);
 int bodyset_force_partials(int which, const float* a, float nu, const GridX& G, const SetArg& P, const float* x0, dim3 grid, double* part, hipStream_t q);
-// force/moment read-out (wl_sim.hip): `partials` writes 3·grid.x Float64 partial sums, then the fixed-order finish, the sum over ranks and the read-back
+// force/moment read-out: `partials` writes 3·grid.x Float64 partial sums, then the fixed-order finish, the sum over ranks and the read-back
 int force_reduce_with(const GridX& G, const RedWs& ws, wl_comm* comm, double* out, hipStream_t q, const std::function<int(dim3, double*, hipStream_t)>& partials);
 }  // namespace wl

@@ -5,21 +5,15 @@
 // The program is a kernel argument (2 KB, kernarg memory): every node field is a scalar load and every branch on it is
 // wave-uniform.  The evaluation stack is per lane, at most WL_BODYSET_STACK entries of (d, n, V) in registers.
 #include <cmath>
+#include <mutex>
 #include <vector>
 
 #include "wl_common.hpp"
 #include "wl_body.hpp"
 #include "wl_bodyset_dev.hpp"
+#include "wl_comm.hpp"
 
 namespace {
-__device__ __forceinline__ bool cell_ij_(const GridX& g, long m, int& i, int& j) {
-  if (m >= g.sz) return false;
-  j = (int)(m / g.nx);
-  i = (int)(m - (long)j * g.nx);
-  return true;
-}
-__device__ __forceinline__ bool interior_ij_(const GridX& g, int i, int j) { return i >= 1 && i <= g.nx - 2 && j >= 1 && j <= g.ny - 2; }
-
 // measure!(flow,body;ϵ)   src/Body.jl:28-51 without the two BC! calls: every element of μ₀, μ₁, V and the interior of σ in one pass
 // (the fill of :29 folded in).  Grid: every plane of the array.
 template <int DS>
@@ -27,11 +21,11 @@ __global__ void __launch_bounds__(WL_BLOCK) k_measure_set(GridX g, float* __rest
   constexpr int D = DS_D, S = DS_S;
   int i, j; long m; int pz;
   wl_tile(g, m, pz);                                      // (the linear order of wl_tile_lin measured slower here: 2.67 against 2.18 ms at 512³)
-  if (!cell_ij_(g, m, i, j)) return;
+  if (!cell_ij(g, m, i, j)) return;
   const int k = pz;
   const long o = m + (long)k * g.sz;
   float m0[3] = {1.f, 1.f, 1.f}, m1[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, vv[3] = {0.f, 0.f, 0.f};
-  if (interior_ij_(g, i, j) && k >= g.k0 && k < g.k1) {
+  if (interior_ij(g, i, j) && k >= g.k0 && k < g.k1) {
     const int I[3] = {i + 1, j + 1, (D == 3) ? g.gk + k + 1 : 1};
     float x[3]; for (int q = 0; q < 3; q++) x[q] = (float)I[q] - 1.5f;
     const float d2 = (2 + e) * (2 + e);
@@ -66,11 +60,32 @@ __global__ void __launch_bounds__(WL_BLOCK) k_pforce_set(GridX g, const float* _
   wl_tile(g, m, pz);
   double acc[3] = {0, 0, 0};
   const int nsl = wl_nslots(g);
-  if (cell_ij_(g, m, i, j) && interior_ij_(g, i, j)) {
+  if (cell_ij(g, m, i, j) && interior_ij(g, i, j)) {
     for (int k = g.k0 + pz; k < g.k1; k += nsl) {
       const int I[3] = {i + 1, j + 1, (D == 3) ? g.gk + k + 1 : 1};
       float x[3]; for (int q = 0; q < 3; q++) x[q] = (float)I[q] - 1.5f;
       float d, n[3], v[3]; set_measure<D, S>(P, x, 1.f, d, n, v);
+      const float kk = kern_(fminf(fmaxf(d, -1.f), 1.f));
+      const float pv = p[m + (long)k * g.sz];
+      float t[3]; pforce_cell<D>(mo.on, mo.x0, pv, n, kk, x, t);
+      for (int a = 0; a < D; a++) acc[a] += (double)t[a];
+    }
+  }
+  const long b = blockIdx.x, nb = gridDim.x;
+  for (int a = 0; a < 3; a++) { const double v = block_sum(acc[a]); if (threadIdx.x == 0) part[a * nb + b] = v; __syncthreads(); }
+}
+// … of a program that is one unmapped sphere or plane (every wl_body): the same terms without the evaluation stack and with the body as a 44-byte argument
+// instead of the 2 KB program — 0.085 against 0.098 ms per read-out at 256³ (profiles/onebody_experiments.md); the viscous sums gain nothing from it
+template <int D>
+__global__ void __launch_bounds__(WL_BLOCK) k_pforce_body(GridX g, const float* __restrict__ p, BodyArg bd, MomArg mo, double* __restrict__ part) {
+  int i, j; long m; int pz;
+  wl_tile(g, m, pz);
+  double acc[3] = {0, 0, 0};
+  const int nsl = wl_nslots(g);
+  if (cell_ij(g, m, i, j) && interior_ij(g, i, j)) {
+    for (int k = g.k0 + pz; k < g.k1; k += nsl) {
+      float x[3]; cell_centre<D>(g, i, j, k, x);
+      float d, n[3]; body_measure<D>(bd, x, 1.f, d, n);
       const float kk = kern_(fminf(fmaxf(d, -1.f), 1.f));
       const float pv = p[m + (long)k * g.sz];
       float t[3]; pforce_cell<D>(mo.on, mo.x0, pv, n, kk, x, t);
@@ -89,7 +104,7 @@ __global__ void __launch_bounds__(WL_BLOCK) k_vforce_set(GridX g, const float* _
   double acc[3] = {0, 0, 0};
   const long st[3] = {1, g.sy, g.sz};
   const int nsl = wl_nslots(g);
-  if (cell_ij_(g, m, i, j) && interior_ij_(g, i, j)) {
+  if (cell_ij(g, m, i, j) && interior_ij(g, i, j)) {
     for (int k = g.k0 + pz; k < g.k1; k += nsl) {
       const int I[3] = {i + 1, j + 1, (D == 3) ? g.gk + k + 1 : 1};
       float x[3]; for (int q = 0; q < 3; q++) x[q] = (float)I[q] - 1.5f;
@@ -103,6 +118,12 @@ __global__ void __launch_bounds__(WL_BLOCK) k_vforce_set(GridX g, const float* _
   const long b = blockIdx.x, nb = gridDim.x;
   for (int a = 0; a < 3; a++) { const double v = block_sum(acc[a]); if (threadIdx.x == 0) part[a * nb + b] = v; __syncthreads(); }
 }
+__global__ void k_fin3(const double* __restrict__ part, int nb, double* __restrict__ out) {
+  for (int a = 0; a < 3; a++) {
+    double s = 0.0; for (int q = threadIdx.x; q < nb; q += WL_BLOCK) s += part[(long)a * nb + q];
+    s = block_sum(s); if (threadIdx.x == 0) out[a] = s; __syncthreads();
+  }
+}
 // measure(body,x;fastd²) at a list of points (x point-major)
 template <int DS>
 __global__ void __launch_bounds__(WL_BLOCK) k_points_set(SetArg P, const float* __restrict__ x, int npts, float fastd2, float* __restrict__ d, float* __restrict__ n, float* __restrict__ v) {
@@ -115,7 +136,6 @@ __global__ void __launch_bounds__(WL_BLOCK) k_points_set(SetArg P, const float* 
   for (int q = 0; q < D; q++) { n[(long)p * D + q] = nn[q]; v[(long)p * D + q] = vv[q]; }
 }
 }  // namespace
-
 
 namespace wl {
 int bodyset_prepare(int D, const wl_bodyset* s, SetArg* out) {
@@ -165,6 +185,20 @@ int bodyset_prepare(int D, const wl_bodyset* s, SetArg* out) {
   out->leaf_root = s->n == 1 ? 1 : 0;
   return 0;
 }
+int bodyset_from_body(int D, const wl_body* b, SetArg* out) {
+  WL_CHECK(b && (b->kind == WL_BODY_SPHERE || b->kind == WL_BODY_PLANE), "wl_body.kind must be WL_BODY_SPHERE or WL_BODY_PLANE");
+  *out = SetArg{};
+  out->n = 1; out->leaf_root = 1; out->depth = 1;
+  wl_body_node& nd = out->node[0];
+  nd.op = WL_OP_LEAF; nd.kind = b->kind; nd.R = b->R;
+  float mm = 0.f;
+  for (int q = 0; q < 3; q++) {
+    nd.c[q] = q < D ? b->c[q] : 0.f; nd.m[q] = q < D ? b->m[q] : 0.f; mm += nd.m[q] * nd.m[q];
+    nd.map.V[q] = (q < D && b->V[q] != 0.f) ? b->V[q] : 0.f;      // (either zero becomes +0: measure! leaves the fill's +0 where the body does not move)
+  }
+  WL_CHECK(mm > 0.f, "wl_body.m (axis mask / plane normal) is zero");
+  return 0;
+}
 int bodyset_measure_fields(float* sigma, float* mu0, float* mu1, float* V, const GridX& G, const SetArg& P, float eps, int exitBC, unsigned perdir, hipStream_t q) {
   BSEL(G.D, P.depth, k_measure_set, wl_plane_grid(G, G.nz), dim3(WL_BLOCK), 0, q, G, sigma, mu0, mu1, V, P, eps);
   WL_LAUNCH_CHECK();
@@ -174,13 +208,39 @@ int bodyset_measure_fields(float* sigma, float* mu0, float* mu1, float* V, const
 }
 int bodyset_force_partials(int which, const float* a, float nu, const GridX& G, const SetArg& P, const float* x0, dim3 grid, double* part, hipStream_t q) {
   MomArg mo{}; if (x0) { mo.on = 1; for (int c = 0; c < G.D; c++) mo.x0[c] = x0[c]; }
-  if (which == 0) { BSEL(G.D, P.depth, k_pforce_set, grid, dim3(WL_BLOCK), 0, q, G, a, P, mo, part); }
+  const wl_body_node& n0 = P.node[0];
+  if (which == 0 && P.leaf_root && !n0.mapped && n0.kind != WL_BODY_CAPSULE) {
+    if (G.D == 3) hipLaunchKernelGGL(k_pforce_body<3>, grid, dim3(WL_BLOCK), 0, q, G, a, body_arg(n0), mo, part);
+    else hipLaunchKernelGGL(k_pforce_body<2>, grid, dim3(WL_BLOCK), 0, q, G, a, body_arg(n0), mo, part);
+  } else if (which == 0) { BSEL(G.D, P.depth, k_pforce_set, grid, dim3(WL_BLOCK), 0, q, G, a, P, mo, part); }
   else { BSEL(G.D, P.depth, k_vforce_set, grid, dim3(WL_BLOCK), 0, q, G, a, nu, P, mo, part); }
   WL_LAUNCH_CHECK();
   return 0;
 }
+// which: 0 pressure_force(p) (src/Metrics.jl:116-133), 1 viscous_force(u,ν) (:140-154); Float64 partial sums, flow.f untouched.
+// On z-slabs every rank sums its own planes and the per-rank sums are added on device (one 128-byte all-gather).
+int force_reduce_with(const GridX& G, const RedWs& ws, wl_comm* comm, double* out, hipStream_t q, const std::function<int(dim3, double*, hipStream_t)>& partials) {
+  const int D = G.D;
+  dim3 grid = wl_plane_grid(G, wl_red_slots(G, G.k1 - G.k0));
+  // partials need 3*grid.x doubles (<= 3*WL_REDPART): pa and pb are contiguous (2*WL_MAXPART doubles)
+  WL_TRY(partials(grid, ws.pa, q));
+  hipLaunchKernelGGL(k_fin3, dim3(1), dim3(WL_BLOCK), 0, q, ws.pa, (int)grid.x, ws.res_d + WL_RD_FORCE);
+  WL_LAUNCH_CHECK();
+  WL_TRY(wl::combine_results(comm, ws, q));
+  std::lock_guard<std::mutex> lock(wl::wl_read_mutex());
+  WlCtx& cx = wl_ctx();
+  WL_HIP(hipMemcpyAsync(cx.h_d, ws.res_d + WL_RD_FORCE, 3 * sizeof(double), hipMemcpyDeviceToHost, q));
+  WL_HIP(hipStreamSynchronize(q));
+  for (int c = 0; c < D; c++) out[c] = cx.h_d[c];
+  return 0;
+}
 }  // namespace wl
 
+// a force (x0 == NULL) or moment of the body program P on the caller's p (which = 0) or u (1), single domain, the library's workspace
+static int force_on_arrays(int which, const float* a, float nu, const GridX& G, const SetArg& P, const float* x0, double* out, void* st) {
+  return wl::force_reduce_with(G, wl_red_ws(wl_ctx().red), nullptr, out, wl_stream(st),
+                               [&](dim3 grid, double* part, hipStream_t q) { return wl::bodyset_force_partials(which, a, nu, G, P, x0, grid, part, q); });
+}
 extern "C" {
 int wl_bodyset_measure_points(const wl_bodyset* set, int D, const float* hx, int npts, float fastd2, float* hd, float* hn, float* hV, void* st) {
   SetArg P; WL_TRY(wl::bodyset_prepare(D, set, &P));
@@ -215,16 +275,35 @@ int wl_pressure_force_bodyset(const float* x0, const float* p, const wl_grid* g,
   WL_CHECK(wl_grid_ok(g) && p && out, "bad wl_grid / p / out");
   SetArg P; WL_TRY(wl::bodyset_prepare(g->D, set, &P));
   WL_TRY(wl_ctx_ensure());
-  const GridX G = gx(*g);
-  return wl::force_reduce_with(G, wl_red_ws(wl_ctx().red), nullptr, out, wl_stream(st),
-                               [&](dim3 grid, double* part, hipStream_t q) { return wl::bodyset_force_partials(0, p, 0.f, G, P, x0, grid, part, q); });
+  return force_on_arrays(0, p, 0.f, gx(*g), P, x0, out, st);
 }
 int wl_viscous_force_bodyset(const float* x0, const float* u, const wl_grid* g, float nu, const wl_bodyset* set, double* out, void* st) {
   WL_CHECK(wl_grid_ok(g) && u && out, "bad wl_grid / u / out");
   SetArg P; WL_TRY(wl::bodyset_prepare(g->D, set, &P));
   WL_TRY(wl_ctx_ensure());
-  const GridX G = gx(*g);
-  return wl::force_reduce_with(G, wl_red_ws(wl_ctx().red), nullptr, out, wl_stream(st),
-                               [&](dim3 grid, double* part, hipStream_t q) { return wl::bodyset_force_partials(1, u, nu, G, P, x0, grid, part, q); });
+  return force_on_arrays(1, u, nu, gx(*g), P, x0, out, st);
+}
+// ---- the closed-form wl_body: the same calls on its one-leaf program
+int wl_measure_body(float* sigma, float* mu0, float* mu1, float* V, const wl_grid* g, const wl_body* body, float eps, int exitBC, uint32_t perdir_mask, void* st) {
+  WL_CHECK(wl_grid_ok(g), "bad wl_grid"); WL_CHECK(sigma && mu0 && mu1 && V, "null field");
+  SetArg P; WL_TRY(wl::bodyset_from_body(g->D, body, &P));
+  return wl::bodyset_measure_fields(sigma, mu0, mu1, V, gx(*g), P, eps, exitBC, perdir_mask, wl_stream(st));
+}
+static int body_force_on_arrays(int which, const float* a, float nu, const wl_grid* g, const wl_body* body, const float* x0, double* out, void* st) {
+  WL_TRY(wl_ctx_ensure());
+  SetArg P; WL_TRY(wl::bodyset_from_body(g->D, body, &P));
+  return force_on_arrays(which, a, nu, gx(*g), P, x0, out, st);
+}
+int wl_pressure_force_body(const float* p, const wl_grid* g, const wl_body* body, double* out, void* st) {
+  WL_CHECK(wl_grid_ok(g), "bad wl_grid"); return body_force_on_arrays(0, p, 0.f, g, body, nullptr, out, st);
+}
+int wl_viscous_force_body(const float* u, const wl_grid* g, float nu, const wl_body* body, double* out, void* st) {
+  WL_CHECK(wl_grid_ok(g), "bad wl_grid"); return body_force_on_arrays(1, u, nu, g, body, nullptr, out, st);
+}
+int wl_pressure_moment_body(const float* x0, const float* p, const wl_grid* g, const wl_body* body, double* out, void* st) {
+  WL_CHECK(wl_grid_ok(g) && x0, "bad wl_grid / x0"); return body_force_on_arrays(0, p, 0.f, g, body, x0, out, st);
+}
+int wl_viscous_moment_body(const float* x0, const float* u, const wl_grid* g, float nu, const wl_body* body, double* out, void* st) {
+  WL_CHECK(wl_grid_ok(g) && x0, "bad wl_grid / x0"); return body_force_on_arrays(1, u, nu, g, body, x0, out, st);
 }
 }  // extern "C"

@@ -46,10 +46,8 @@ __device__ __forceinline__ float leaf_sdf(const wl_body_node& b, const float* x)
 template <int D>
 __device__ __forceinline__ void leaf_measure(const wl_body_node& b, const float* x, float fastd2, float& d, float* n, float* v) {
   for (int q = 0; q < 3; q++) { n[q] = 0.f; v[q] = 0.f; }
-  if (!b.mapped && b.kind != WL_BODY_CAPSULE) {          // exactly wl_body's measure (V = 0)
-    BodyArg ba; ba.kind = b.kind; ba.R = b.R;
-    for (int q = 0; q < 3; q++) { ba.c[q] = b.c[q]; ba.m[q] = b.m[q]; ba.V[q] = 0.f; }
-    body_measure<D>(ba, x, fastd2, d, n);
+  if (!b.mapped && b.kind != WL_BODY_CAPSULE) {          // the closed-form wl_body: V = its translation velocity (wl::bodyset_from_body; 0 in every public program)
+    if (body_measure<D>(body_arg(b), x, fastd2, d, n)) for (int q = 0; q < D; q++) v[q] = b.map.V[q];
     return;
   }
   float xi[3] = {x[0], x[1], x[2]}, bq[3] = {0.f, 0.f, 0.f};

@@ -124,6 +124,14 @@ __device__ __forceinline__ bool wl_tile_lin(const GridX& g, long& m, int& p) {
   m = bx * WL_BLOCK + threadIdx.x;
   return bx < nbx;
 }
+// the in-plane index m of wl_tile as (i, j), 0-based array indices; false beyond the plane.  interior_ij: not a ghost cell of the plane
+__device__ __forceinline__ bool cell_ij(const GridX& g, long m, int& i, int& j) {
+  if (m >= g.sz) return false;
+  j = (int)(m / g.nx);
+  i = (int)(m - (long)j * g.nx);
+  return true;
+}
+__device__ __forceinline__ bool interior_ij(const GridX& g, int i, int j) { return i >= 1 && i <= g.nx - 2 && j >= 1 && j <= g.ny - 2; }
 __device__ __forceinline__ int wl_nslots(const GridX& g) {   // number of plane slots of this launch
   const long nbx = (g.sz + WL_BLOCK - 1) / WL_BLOCK;
   return (int)(gridDim.x / (8u * (unsigned)((nbx + 7) >> 3)));
@@ -288,6 +296,12 @@ bool conv_z_ok(const GridX& g, unsigned per);
 int conv_diff_z(float* f, const float* u_adv, const float* u0, const float* mu0, float* u_out, const GridX& g, float nu, int scheme, float dt, float pre, float post, hipStream_t s);
 int bdim(float* u, const float* u0, float* f, const float* V, const float* mu0, const float* mu1, const GridX& g, float dt, float pre, float post, hipStream_t s);
 int accelerate(float* r, const GridX& g, const float* a, hipStream_t s);
+// exitBC!(u,u⁰,Δt) (wl_exit.hip): the whole x-exit face on this rank (sc: two doubles of workspace) / on z-slabs this rank's planes summed into *sum, then —
+// once the caller has added the ranks' sums — the global mean into sc and the update of this rank's planes; mode 0 the convective update, 1 the flux correction
+int exit_bc_single(const GridX& G, float* u, const float* u0, double* sc, float dt, hipStream_t s);
+int exit_bc_slab_sum(const GridX& G, const float* u, double* sum, int mode, hipStream_t s);
+int exit_bc_slab_update(const GridX& G, float* u, const float* u0, const double* gsum, double* sc, float dt, int mode, hipStream_t s);
+int copy_exit_face(float* dst, const float* src, const GridX& G, hipStream_t s);      // the exit face travels with the role when the velocity buffers rotate
 int sgs(float* f, float* sigma, const float* u, const GridX& g, float Cs, float Delta, hipStream_t s);   // sgs! with the Smagorinsky–Lilly νₜ (wl_sgs.hip): 3-D single domain, else WL_EINVAL
 // flow diagnostics of src/Metrics.jl:27-109 (wl_metrics.hip): single-domain grids only, ω-family and λ₂ 3-D only, else WL_EINVAL before any launch
 int metrics_fields(const float* u, const GridX& g, const float* U, float* ke, float* w3, float* wmag, float* l2, hipStream_t s);   // one launch; null outputs are skipped

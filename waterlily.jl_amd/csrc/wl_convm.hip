@@ -9,18 +9,13 @@
 #include "wl_conv_cell.hpp"
 
 namespace {
-__device__ __forceinline__ bool cm_cell_ij(const GridX& g, long m, int& i, int& j) {
-  if (m >= g.sz) return false;
-  j = (int)(m / g.nx); i = (int)(m - (long)j * g.nx);
-  return true;
-}
 int g_convm_on = 0;   // measured 6 % SLOWER than the plane kernel at 512³ (120 VGPRs → 4 waves/SIMD): opt-in (wl_sim_set_option("convm",1))
 
 template <int SCH, int PER, int FUSE>
 __global__ void __launch_bounds__(WL_BLOCK) k_conv_march(GridX g, float* __restrict__ r, const float* __restrict__ u, float nu, unsigned per, int kfirst, int klast, int zchunk, BdimArgs bd) {
   int i, j; long m; int pz;
   wl_tile(g, m, pz);
-  if (!cm_cell_ij(g, m, i, j)) return;
+  if (!cell_ij(g, m, i, j)) return;
   const int ks = kfirst + pz * zchunk, ke = (ks + zchunk < klast) ? ks + zchunk : klast;
   if (ks >= ke) return;
   const int N[3] = {g.nx, g.ny, g.gnz};

@@ -13,14 +13,6 @@
 
 namespace {
 
-__device__ __forceinline__ bool cell_ij(const GridX& g, long m, int& i, int& j) {
-  if (m >= g.sz) return false;
-  j = (int)(m / g.nx);
-  i = (int)(m - (long)j * g.nx);
-  return true;
-}
-__device__ __forceinline__ bool interior_ij(const GridX& g, int i, int j) { return i >= 1 && i <= g.nx - 2 && j >= 1 && j <= g.ny - 2; }
-
 // ---- generic ------------------------------------------------------------------------------------
 __global__ void k_fill(float* __restrict__ a, float v, size_t n) {
   for (size_t q = (size_t)blockIdx.x * WL_BLOCK + threadIdx.x; q < n; q += (size_t)gridDim.x * WL_BLOCK) a[q] = v;
@@ -65,6 +57,18 @@ __global__ void k_red_dot(const float* __restrict__ a, const float* __restrict__
 __global__ void k_fin_sum(const double* __restrict__ part, int n, double* __restrict__ out) {
   double a = 0.0; for (int q = threadIdx.x; q < n; q += WL_BLOCK) a += part[q];
   a = block_sum(a); if (threadIdx.x == 0) *out = a;
+}
+// L₂(a) = Σ_inside a² in Float64 (src/util.jl:57), partial sums per block
+template <int D>
+__global__ void k_l2_inside(GridX g, const float* __restrict__ a, double* __restrict__ part) {
+  int i, j; long m; int pz;
+  wl_tile(g, m, pz);
+  double acc = 0.0;
+  const int nsl = wl_nslots(g);
+  if (cell_ij(g, m, i, j) && interior_ij(g, i, j))
+    for (int k = g.k0 + pz; k < g.k1; k += nsl) { const double v = (double)a[m + (long)k * g.sz]; acc += v * v; }
+  acc = block_sum(acc);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 __global__ void k_fin_sum_max(const double* __restrict__ part, const float* __restrict__ pmax, int n, double* __restrict__ os, float* __restrict__ om) {
   double a = 0.0; float mx = -INFINITY;
@@ -930,3 +934,20 @@ int cfl_dev(const float* u, float* sigma, const GridX& g, const RedWs& ws, int s
   WL_LAUNCH_CHECK(); return 0;
 }
 }  // namespace wl
+
+extern "C" {
+int wl_L2_inside(const float* a, const wl_grid* g, double* out, void* st) {
+  WL_CHECK(wl_grid_ok(g), "bad wl_grid"); WL_TRY(wl_ctx_ensure());
+  const GridX G = gx(*g); hipStream_t s = wl_stream(st);
+  const RedWs ws = wl_red_ws(wl_ctx().red);
+  dim3 grid = wl_plane_grid(G, wl_red_slots(G, G.k1 - G.k0));
+  DSEL(G.D, k_l2_inside, grid, dim3(WL_BLOCK), 0, s, G, a, ws.pa);
+  hipLaunchKernelGGL(k_fin_sum, dim3(1), dim3(WL_BLOCK), 0, s, ws.pa, (int)grid.x, ws.res_d + WL_RD_SUM);
+  WL_LAUNCH_CHECK();
+  return wl::read_results(ws, out, wl_upto(WL_RD_SUM), nullptr, 0, s);
+}
+int wl_accelerate(float* r, const wl_grid* g, const float* a, void* st) {
+  WL_CHECK(wl_grid_ok(g) && a, "bad argument"); WL_TRY(wl_ctx_ensure());
+  return wl::accelerate(r, gx(*g), a, wl_stream(st));
+}
+}  // extern "C"

@@ -11,14 +11,6 @@
 
 namespace {
 
-__device__ __forceinline__ bool cell_ij(const GridX& g, long m, int& i, int& j) {
-  if (m >= g.sz) return false;
-  j = (int)(m / g.nx);
-  i = (int)(m - (long)j * g.nx);
-  return true;
-}
-__device__ __forceinline__ bool interior_ij(const GridX& g, int i, int j) { return i >= 1 && i <= g.nx - 2 && j >= 1 && j <= g.ny - 2; }
-
 // mult(I,L,D,x)   src/Poisson.jl:70-76
 template <int D>
 __device__ __forceinline__ float Ax(const GridX& g, long o, const float* __restrict__ L, const float* __restrict__ Dg, const float* __restrict__ x) {

@@ -1,6 +1,5 @@
-// Simulation/Flow composite handle: mom_step! orchestration (src/Flow.jl:156-237) on one HIP stream,
-// plus the device-side input generators / read-outs used by the configs (TGV initial condition,
-// closed-form sphere measure!, pressure_force) and exitBC!, L₂.
+// Simulation/Flow composite handle: mom_step! orchestration (src/Flow.jl:156-237) on one HIP stream and the handle's life cycle, plus the
+// TGV / uniform initial conditions.  Bodies: wl_bodyset.hip; observers of a step: wl_observe.hip; exitBC!'s kernels: wl_exit.hip.
 #include <cmath>
 #include <cstring>
 #include <utility>
@@ -13,16 +12,9 @@
 #include "wl_pdefer.hpp"
 #include "wl_forces.hpp"
 #include "wl_meanflow.hpp"
+#include "wl_observe.hpp"
 
 namespace {
-__device__ __forceinline__ bool cell_ij(const GridX& g, long m, int& i, int& j) {
-  if (m >= g.sz) return false;
-  j = (int)(m / g.nx);
-  i = (int)(m - (long)j * g.nx);
-  return true;
-}
-__device__ __forceinline__ bool interior_ij(const GridX& g, int i, int j) { return i >= 1 && i <= g.nx - 2 && j >= 1 && j <= g.ny - 2; }
-
 // apply!(u0,u): u[I,i] = u0(i, loc(i,I))   src/Flow.jl:81-83, loc src/core.jl:177 (Float32)
 // kind 1: wall-bounded TGV κ=π/N ; kind 2: periodic TGV κ=2π/N  
 template <int D>
@@ -53,201 +45,8 @@ __global__ void k_apply_const(GridX g, float* __restrict__ u, float U0, float U1
   u[o] = U0; u[g.cs + o] = U1; if (D == 3) u[2 * g.cs + o] = U2;
 }
 
-// measure!(flow,body;ϵ) for the sphere: fills σ(sdf), μ₀, μ₁, V(=0) on the interior   src/Body.jl:28-48
-template <int D>
-__global__ void k_measure_body(GridX g, float* __restrict__ sig, float* __restrict__ mu0, float* __restrict__ mu1, float* __restrict__ V, BodyArg bd, float e) {
-  int i, j; long m; int pz;
-  wl_tile(g, m, pz);
-  if (!cell_ij(g, m, i, j) || !interior_ij(g, i, j)) return;
-  const int k = g.k0 + pz;
-  const long o = m + (long)k * g.sz;
-  const int I[3] = {i + 1, j + 1, (D == 3) ? g.gk + k + 1 : 1};
-  float x[3]; for (int q = 0; q < 3; q++) x[q] = (float)I[q] - 1.5f;
-  const float dc = body_sdf<D>(bd, x);
-  sig[o] = dc;
-  const float d2 = (2 + e) * (2 + e);
-  if (dc * dc < d2) {
-    for (int a = 0; a < D; a++) {
-      float xf[3]; for (int q = 0; q < 3; q++) xf[q] = x[q] - ((q == a) ? 0.5f : 0.f);
-      float di, ni[3]; const bool full = body_measure<D>(bd, xf, d2, di, ni);
-      di = fabsf(di) <= 0.5f ? di : copysignf(di, dc);
-      if (full && bd.V[a] != 0.f) V[(long)a * g.cs + o] = bd.V[a];       // (V was zero-filled: Body.jl:29)
-      mu0[(long)a * g.cs + o] = mu0_(di, e);
-      for (int b = 0; b < D; b++) mu1[(long)(a + b * D) * g.cs + o] = mu1_(di, e) * ni[b];
-    }
-  } else if (dc < 0.f) {
-    for (int a = 0; a < D; a++) mu0[(long)a * g.cs + o] = 0.f;
-  }
-}
-// pressure_force: Σ_inside p[I]·n·kern(clamp(d,-1,1)) in Float64   src/Metrics.jl:116-133
-template <int D>
-__global__ void k_pforce_body(GridX g, const float* __restrict__ p, BodyArg bd, MomArg mo, double* __restrict__ part) {
-  int i, j; long m; int pz;
-  wl_tile(g, m, pz);
-  double acc[3] = {0, 0, 0};
-  const int nsl = wl_nslots(g);
-  if (cell_ij(g, m, i, j) && interior_ij(g, i, j)) {
-    for (int k = g.k0 + pz; k < g.k1; k += nsl) {
-      const int I[3] = {i + 1, j + 1, (D == 3) ? g.gk + k + 1 : 1};
-      float x[3]; for (int q = 0; q < 3; q++) x[q] = (float)I[q] - 1.5f;
-      float d, n[3]; body_measure<D>(bd, x, 1.f, d, n);
-      const float kk = kern_(fminf(fmaxf(d, -1.f), 1.f));
-      const float pv = p[m + (long)k * g.sz];
-      if (mo.on) {
-        float nds[3] = {0.f, 0.f, 0.f}, rr[3] = {0.f, 0.f, 0.f}, cr[3];
-        for (int a = 0; a < D; a++) { nds[a] = n[a] * kk; rr[a] = x[a] - mo.x0[a]; }
-        cross_<D>(rr, nds, cr);
-        for (int a = 0; a < D; a++) acc[a] += (double)(pv * cr[a]);
-      } else {
-        for (int a = 0; a < D; a++) acc[a] += (double)(pv * (n[a] * kk));
-      }
-    }
-  }
-  const long b = blockIdx.x, nb = gridDim.x;
-  for (int a = 0; a < 3; a++) { const double v = block_sum(acc[a]); if (threadIdx.x == 0) part[a * nb + b] = v; __syncthreads(); }
-}
-// viscous_force: Σ_inside −2ν·S(I,u)·n·kern(clamp(d,-1,1)) in Float64   src/Metrics.jl:140-154, ∂(i,j,I,u) :42-44
-template <int D>
-__global__ void k_vforce_body(GridX g, const float* __restrict__ u, float nu, BodyArg bd, MomArg mo, double* __restrict__ part) {
-  int i, j; long m; int pz;
-  wl_tile(g, m, pz);
-  double acc[3] = {0, 0, 0};
-  const long st[3] = {1, g.sy, g.sz};
-  const int nsl = wl_nslots(g);
-  if (cell_ij(g, m, i, j) && interior_ij(g, i, j)) {
-    for (int k = g.k0 + pz; k < g.k1; k += nsl) {
-      const int I[3] = {i + 1, j + 1, (D == 3) ? g.gk + k + 1 : 1};
-      float x[3]; for (int q = 0; q < 3; q++) x[q] = (float)I[q] - 1.5f;
-      float d, n[3]; body_measure<D>(bd, x, 1.f, d, n);
-      const float kk = kern_(fminf(fmaxf(d, -1.f), 1.f));
-      const long o = m + (long)k * g.sz;
-      auto du = [&](int a, int b) -> float {       // ∂u_a/∂x_b at the cell centre
-        const float* __restrict__ f = u + (long)a * g.cs;
-        if (a == b) return f[o + st[a]] - f[o];
-        return (f[o + st[b]] + f[o + st[b] + st[a]] - f[o - st[b]] - f[o - st[b] + st[a]]) / 4;
-      };
-      if (mo.on) {
-        float sn[3] = {0.f, 0.f, 0.f}, rr[3] = {0.f, 0.f, 0.f}, cr[3];
-        for (int a = 0; a < D; a++) {
-          float v = 0.f;
-          for (int b = 0; b < D; b++) { const float Sab = (du(a, b) + du(b, a)) / 2; v += Sab * (n[b] * kk); }
-          sn[a] = v; rr[a] = x[a] - mo.x0[a];
-        }
-        cross_<D>(rr, sn, cr);
-        for (int a = 0; a < D; a++) acc[a] += (double)((-2 * nu) * cr[a]);
-      } else {
-        for (int a = 0; a < D; a++) {
-          float v = 0.f;
-          for (int b = 0; b < D; b++) { const float Sab = (du(a, b) + du(b, a)) / 2; v += ((-2 * nu) * Sab) * (n[b] * kk); }
-          acc[a] += (double)v;
-        }
-      }
-    }
-  }
-  const long b = blockIdx.x, nb = gridDim.x;
-  for (int a = 0; a < 3; a++) { const double v = block_sum(acc[a]); if (threadIdx.x == 0) part[a * nb + b] = v; __syncthreads(); }
-}
-__global__ void k_fin3(const double* __restrict__ part, int nb, double* __restrict__ out) {
-  for (int a = 0; a < 3; a++) {
-    double s = 0.0; for (int q = threadIdx.x; q < nb; q += WL_BLOCK) s += part[(long)a * nb + q];
-    s = block_sum(s); if (threadIdx.x == 0) out[a] = s; __syncthreads();
-  }
-}
-template <int D>
-__global__ void k_l2_inside(GridX g, const float* __restrict__ a, double* __restrict__ part) {
-  int i, j; long m; int pz;
-  wl_tile(g, m, pz);
-  double acc = 0.0;
-  const int nsl = wl_nslots(g);
-  if (cell_ij(g, m, i, j) && interior_ij(g, i, j))
-    for (int k = g.k0 + pz; k < g.k1; k += nsl) { const double v = (double)a[m + (long)k * g.sz]; acc += v * v; }
-  acc = block_sum(acc);
-  if (threadIdx.x == 0) part[blockIdx.x] = acc;
-}
-__global__ void k_fin1(const double* __restrict__ part, int n, double* __restrict__ out) {
-  double a = 0.0; for (int q = threadIdx.x; q < n; q += WL_BLOCK) a += part[q];
-  a = block_sum(a); if (threadIdx.x == 0) *out = a;
-}
-
-// exitBC!(u,u⁰,Δt)   src/core.jl:226-233 — single-domain; face sums by one block (deterministic), all on device
-// mode 0: out[0] = Σ u[2, 2:N-1.., 1]/len (inflow) ; mode 1: out[1] = Σ u[N, ..,1]/len − out[0]
-template <int D>
-__global__ void k_exit_facesum(GridX g, const float* __restrict__ u, double* __restrict__ out, int mode) {
-  const int ny = g.ny - 2, nz = (D == 3) ? (g.nz - 2) : 1;
-  const long cnt = (long)ny * nz;
-  const int ix = (mode == 0) ? 1 : g.nx - 1;
-  double acc = 0.0;
-  for (long q = threadIdx.x; q < cnt; q += blockDim.x) {
-    const int j = 1 + (int)(q % ny), k = (D == 3) ? 1 + (int)(q / ny) : 0;
-    acc += (double)u[ix + (long)j * g.sy + (long)k * g.sz];
-  }
-  __shared__ double sh[16];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0; for (int w = 0; w < (int)(blockDim.x >> 6); w++) s += sh[w];
-    const float mean = (float)s / (float)cnt;
-    if (mode == 0) out[0] = (double)mean; else out[1] = (double)(mean - (float)out[0]);
-  }
-}
-// The x-exit face of the normal component (Julia index N of u[:,:,:,1], every row and plane): with the convective exit BC! leaves it alone
-// (saveexit, src/core.jl:207) and only exitBC! rewrites its interior rows — so when the roles of the velocity buffers rotate instead of
-// `u⁰ .= u` being a copy, the face has to travel with the role.
-template <int D>
-__global__ void k_copy_exit_face(GridX g, float* __restrict__ dst, const float* __restrict__ src) {
-  const long cnt = (long)g.ny * (D == 3 ? g.nz : 1);
-  const long q = (long)blockIdx.x * WL_BLOCK + threadIdx.x;
-  if (q >= cnt) return;
-  const long o = (g.nx - 1) + q * g.sy;      // (rows are contiguous over planes: j + k·ny)
-  dst[o] = src[o];
-}
-// z-slab variant: every rank sums its owned planes of the face (res_d[slot], summed over ranks by combine_results), then
-// k_exit_mean turns the global sum into the mean exactly as above (float division by the global face size)
-template <int D>
-__global__ void k_exit_facesum_part(GridX g, const float* __restrict__ u, double* __restrict__ out, int mode) {
-  const int ny = g.ny - 2, nz = g.k1 - g.k0;
-  const long cnt = (long)ny * nz;
-  const int ix = (mode == 0) ? 1 : g.nx - 1;
-  double acc = 0.0;
-  for (long q = threadIdx.x; q < cnt; q += blockDim.x) {
-    const int j = 1 + (int)(q % ny), k = g.k0 + (int)(q / ny);
-    acc += (double)u[ix + (long)j * g.sy + (long)k * g.sz];
-  }
-  __shared__ double sh[16];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) { double s = 0.0; for (int w = 0; w < (int)(blockDim.x >> 6); w++) s += sh[w]; *out = s; }
-}
-__global__ void k_exit_mean(const double* __restrict__ gsum, double* __restrict__ sc, long cnt, int mode) {
-  const float mean = (float)(*gsum) / (float)cnt;
-  if (mode == 0) sc[0] = (double)mean; else sc[1] = (double)(mean - (float)sc[0]);
-}
-template <int D>
-__global__ void k_exit_update_slab(GridX g, float* __restrict__ u, const float* __restrict__ u0, const double* __restrict__ sc, float dt, int mode) {
-  const int ny = g.ny - 2;
-  const long cnt = (long)ny * (g.k1 - g.k0);
-  const long q = (long)blockIdx.x * WL_BLOCK + threadIdx.x;
-  if (q >= cnt) return;
-  const int j = 1 + (int)(q % ny), k = g.k0 + (int)(q / ny);
-  const long o = (g.nx - 1) + (long)j * g.sy + (long)k * g.sz;
-  if (mode == 0) { const float U = (float)sc[0]; u[o] = u0[o] - U * dt * (u0[o] - u0[o - 1]); }
-  else u[o] -= (float)sc[1];
-}
 // Δt = min(10, 1/(max σ + 5ν))  (src/Flow.jl:166, CFL :234-237) on the device: the statement wl_sim::cfl evaluates on the host from the same maximum
 __global__ void k_dt_from_cfl(float* __restrict__ res_f, int in_slot, int out_slot, float nu) { res_f[out_slot] = fminf(10.f, 1.0f / (res_f[in_slot] + 5 * nu)); }
-template <int D>
-__global__ void k_exit_update(GridX g, float* __restrict__ u, const float* __restrict__ u0, const double* __restrict__ sc, float dt, int mode) {
-  const int ny = g.ny - 2;
-  const long cnt = (long)ny * ((D == 3) ? (g.nz - 2) : 1);
-  const long q = (long)blockIdx.x * WL_BLOCK + threadIdx.x;
-  if (q >= cnt) return;
-  const int j = 1 + (int)(q % ny), k = (D == 3) ? 1 + (int)(q / ny) : 0;
-  const long o = (g.nx - 1) + (long)j * g.sy + (long)k * g.sz;
-  if (mode == 0) { const float U = (float)sc[0]; u[o] = u0[o] - U * dt * (u0[o] - u0[o - 1]); }
-  else u[o] -= (float)sc[1];
-}
 }  // namespace
 
 #define DSEL(D, KERN, ...)                                                           \
@@ -290,7 +89,7 @@ struct wl_sim {
   // makes memory current for a reader outside the step (fields handed out, force read-outs, wl_sim_phase, a failed step).  Between calls nothing is pending but, on
   // slabs, the exchange — "a call never returns with the divisor pending", every projection ends with BC! applied — so this launches nothing there.
   int settle(hipStream_t s) { WL_TRY(sync_u(s)); WL_TRY(materialise_p(s)); return flush_bc(s); }
-  ~wl_sim() { if (df.u_pending && comm && comm->cs) (void)hipStreamSynchronize(comm->cs); if (own_mg) delete mg; if (own) (void)hipFree(own); if (exit_sc) (void)hipFree(exit_sc); if (farmask) (void)hipFree(farmask); if (mnear) (void)hipFree(mnear); if (mneedf) (void)hipFree(mneedf); if (mm0var) (void)hipFree(mm0var); free_probes(); free_tracers(); free_forces(); free_mean(); fimm.release(); }
+  ~wl_sim() { if (df.u_pending && comm && comm->cs) (void)hipStreamSynchronize(comm->cs); if (own_mg) delete mg; if (own) (void)hipFree(own); if (exit_sc) (void)hipFree(exit_sc); if (farmask) (void)hipFree(farmask); if (mnear) (void)hipFree(mnear); if (mneedf) (void)hipFree(mneedf); if (mm0var) (void)hipFree(mm0var); }
 
   // BC!(u) on the physical faces this rank holds, then the z-halo planes (depth 2: QUICK reads f[I-2δ], src/Flow.jl:8)
   // On slabs the exchange runs on the communicator's own stream; the compute stream waits for it (sync_u) only where the halo
@@ -398,9 +197,8 @@ struct wl_sim {
     }
     return wl::bdim(u, u0, f, nullptr, mu0, nullptr, G, dt.back(), pre, post, s);
   }
-  int exit_bc(hipStream_t s);
-  static int exit_bc_single(const GridX& G, float* u, const float* u0, double* sc, float dt, hipStream_t s);   // (also behind wl_exit_bc)
-  int copy_exit_face(float* dst, const float* src, hipStream_t s);
+  int exit_bc(hipStream_t s);      // (kernels and the single-domain form: wl_exit.hip)
+  int copy_exit_face(float* dst, const float* src, hipStream_t s) { return wl::copy_exit_face(dst, src, G, s); }
   // BC!(u,U) after the fused conv_diff!+BDIM! DEFERRED inside mom_step! (option "bcdefer", df.bc_deferred): until the projection's tail rewrites every boundary
   // location through its folded stores, boundary locations are read only where a component is normal to the face, where BC! writes the constant U — the fused
   // head and the pair tail substitute U on load (wl_resjac_body.inc, k_project_cfl2) and the two k_bc_vec launches per step (2 × 0.07 ms at 512³: strided x
@@ -543,7 +341,7 @@ struct wl_sim {
   }
   bool skip_p_now(const ProjCall& c) const {      // decided per launch: a back-off during the head withdraws it
     if (!pdefer_ok()) return false;
-    if (c.with_cfl) return c.step_follows && !probe_m && !force_on && !mean_due();   // the corrector's tail: the next reader is the next step's head — unless the probe or force record or the mean-flow update of this step reads p first
+    if (c.with_cfl) return c.step_follows && !obs.reads_p_after_this_step();   // the corrector's tail: the next reader is the next step's head — unless an observer of this step reads p first
     return c.corrector_follows && (!p_home || c.step_follows || p == p_home);   // the predictor's tail: the corrector's head (caller-owned p, last step of the call: see the parity rule above)
   }
   // go != nullptr: queued inside the solver loop ahead of its read — runs iff the flag says "converged"; a gated tail that was withheld is launched again with go = nullptr.
@@ -694,90 +492,14 @@ struct wl_sim {
     dt.push_back(std::fmin(10.f, 1.0f / (mx + 5 * d.nu)));
     return 0;
   }
-  // ---- observers of a completed step (wl_sim_set_probes, wl_sim_set_tracers; kernels in wl_interp.hip).  Both read the step's final u — and the probes p, the tracers
-  // the array in the u⁰ role, which no kernel of the step writes: it still holds the velocity the step started from (src/Flow.jl:157) — after the second projection
-  // and before CFL; neither writes anything the step reads, so a handle with observers computes the bits of one without.  One launch each per step, none when unset.
-  float *probe_x = nullptr, *probe_rec = nullptr;      // device: m×D points; capacity records of m×(D+1) floats
-  int probe_m = 0, probe_cap = 0, probe_n = 0;         // probes, records the buffer takes, records held
-  long probe_first = 0, n_probe_dropped = 0;           // index into Δt of the first held record's step; records a full buffer refused
-  float *tr_x = nullptr, *tr_x0 = nullptr; size_t tr_n = 0;      // tracer positions and positions before the last step (n×D each)
-  hipStream_t obs_stream = nullptr;                    // the stream the last record went to (wl_sim_read_probes waits for it)
+  // ---- observers of a completed step (wl_observe.hpp): probe and force records, tracers, the mean flow.  One member; the step asks it one question (skip_p_now)
+  // and calls it once, after the second projection and before CFL
+  wl::Observers obs;
   long n_step_launches = 0;                            // kernel launches of this handle's mom_step! calls (wl_sim_counter "launches")
-  void free_probes() { if (probe_x) (void)hipFree(probe_x); if (probe_rec) (void)hipFree(probe_rec); probe_x = probe_rec = nullptr; probe_m = probe_cap = probe_n = 0; }
-  // the force recorder (wl_sim_set_force_record; kernels in wl_forces.hip): after every completed step 12 doubles — pressure force, viscous force, pressure and
-  // viscous moment about force_x0 — of the recorder's body on the step's final p and u, from the body's band only.  Two launches per step (one for an empty
-  // band), no host round trip.  fimm: the band of the immediate read-out wl_sim_forces_bodyset, kept so that a repeated call finds its list built.
-  wl::ForceBand fband, fimm;
-  bool force_on = false;
-  float force_x0[3] = {0.f, 0.f, 0.f};
-  double* force_rec = nullptr;                         // device: capacity records of 12 doubles
-  int force_cap = 0, force_n = 0;
-  long force_first = 0, n_force_dropped = 0;
-  hipStream_t force_stream = nullptr;                  // the stream the last record went to (wl_sim_read_forces waits for it)
-  void free_forces() { if (force_rec) (void)hipFree(force_rec); force_rec = nullptr; force_cap = force_n = 0; force_on = false; fband.release(); }
-  // measure!(sim) replaced the body: pressure_force(sim) always means sim.body as it is now, so the recorder follows it
-  int force_body_changed(const SetArg& P, hipStream_t s) { return force_on ? fband.build(G, P, s) : 0; }
-  // the mean-flow observer (wl_sim_set_meanflow; kernels in wl_meanflow.hip): MeanFlow's P, U and — mode 2 — UU = ⟨u⊗u⟩ (src/Metrics.jl:205-262), updated by ONE
-  // launch after every mean_every-th completed step on the step's final p and u, every cell of the arrays.  ε and the time vector are update!'s Float32
-  // statements on the host (:237-239,247); time(flow) is the in-order sum of the Δt history, this step's Δt included — what wl_sim_time returns once cfl has
-  // appended the next one.  UU is packed (i ≤ j: wl_meanflow.hip).  Steps on which no update is due launch nothing and defer as a handle without the observer.
-  float* mean_own = nullptr;                           // device: P (cs) | U (D·cs) | packed UU (D(D+1)/2·cs, mode 2), zero-initialised
-  int mean_mode = 0, mean_every = 1;                   // 0 off, 1 P and U, 2 with UU; an update every mean_every-th completed step
-  long mean_steps = 0, n_mean_updates = 0;             // completed steps since set/reset; updates since set
-  std::vector<float> mean_t;                           // meanflow.t
-  hipStream_t mean_stream = nullptr;                   // the stream the last update or reset went to (wl_sim_set_meanflow waits for it before it frees)
-  float* mean_P() const { return mean_own; }
-  float* mean_U() const { return mean_own ? mean_own + (size_t)G.cs : nullptr; }
-  float* mean_UU() const { return mean_own && mean_mode == 2 ? mean_own + (size_t)G.cs * (size_t)(1 + d.D) : nullptr; }
-  size_t mean_floats(int mode) const { return (size_t)G.cs * (size_t)(1 + d.D + (mode == 2 ? wl::meanflow_packed_planes(d.D) : 0)); }
-  void free_mean() { if (mean_own) (void)hipFree(mean_own); mean_own = nullptr; mean_mode = 0; mean_every = 1; mean_steps = 0; mean_t.clear(); }
-  bool mean_due() const { return mean_mode && (mean_steps + 1) % mean_every == 0; }      // the step now running (or the next one) ends with an update
-  float time_f(size_t n_dt) const { float t = 0.f; for (size_t k = 0; k < n_dt; k++) t += dt[k]; return t; }      // Float32, in order: sum(Δt[1:n])
-  int mean_reset(float t_init, hipStream_t s) {        // reset!(meanflow; t_init) :229-234
-    WL_HIP(hipMemsetAsync(mean_own, 0, mean_floats(mean_mode) * sizeof(float), s));
-    mean_t.assign(1, t_init); mean_steps = 0; mean_stream = s;
-    return 0;
-  }
-  int mean_update(float t_flow, hipStream_t s) {       // update!(meanflow, flow) :236-248 with time(flow) = t_flow; p is current (the callers see to that)
-    const float dtm = t_flow - mean_t.back();
-    float e = dtm / (dtm + (mean_t.back() - mean_t.front()) + 1.1920929e-7f);
-    if (mean_t.size() == 1) e = 1.f;                   // the first update takes the instantaneous field
-    WL_TRY(wl::meanflow_observe(mean_P(), mean_U(), mean_UU(), p, u, G, e, s));
-    mean_t.push_back(mean_t.back() + dtm);
-    n_mean_updates++; mean_stream = s;
-    return 0;
-  }
-  void free_tracers() { if (tr_x) (void)hipFree(tr_x); if (tr_x0) (void)hipFree(tr_x0); tr_x = tr_x0 = nullptr; tr_n = 0; }
+  wl::StepView view() const { return {G, d.D, u, u0, p, d.nu, dt, d.perdir_mask}; }      // (the roles rotate: taken where it is used)
   int observe(hipStream_t s) {      // dt.back() is still the Δt this step ran with: cfl appends the next one afterwards
-    if (probe_m) {
-      WL_TRY(materialise_p(s));     // (guard: skip_p_now keeps the corrector's tail storing while probes are set)
-      if (probe_n == probe_cap) n_probe_dropped++;
-      else {
-        float* rec = probe_rec + (size_t)probe_n * probe_m * (d.D + 1);
-        WL_TRY(wl::interp_points(u, p, G, probe_x, (size_t)probe_m, rec, d.D + 1, rec + d.D, d.D + 1, s));
-        if (probe_n++ == 0) probe_first = (long)dt.size() - 1;
-        obs_stream = s;
-      }
-    }
-    if (force_on) {
-      WL_TRY(materialise_p(s));     // (guard, as above)
-      if (force_n == force_cap) n_force_dropped++;
-      else {
-        WL_TRY(fband.run(G, p, u, d.nu, force_x0, force_rec + (size_t)force_n * 12, s));
-        if (force_n++ == 0) force_first = (long)dt.size() - 1;
-        force_stream = s;
-      }
-    }
-    if (tr_n) WL_TRY(wl::advect(tr_x, tr_x0, u0, u, G, tr_n, dt.back(), d.perdir_mask, s));
-    if (mean_mode) {
-      const bool due = mean_due();
-      mean_steps++;
-      if (due) {
-        WL_TRY(materialise_p(s));   // (guard, as above)
-        WL_TRY(mean_update(time_f(dt.size()), s));
-      }
-    }
-    return 0;
+    if (obs.reads_p_after_this_step()) WL_TRY(materialise_p(s));     // (guard: skip_p_now keeps the corrector's tail storing on such a step)
+    return obs.after_step(view(), s);
   }
   int mom_step(hipStream_t s, bool more_follow = false) {
     const long l0 = g_wl_launches;
@@ -815,57 +537,21 @@ struct wl_sim {
     return cfl(s, more_follow);
   }
 };
-int wl_sim::copy_exit_face(float* dst, const float* src, hipStream_t s) {
-  const long cnt = (long)G.ny * (G.D == 3 ? G.nz : 1);
-  DSEL(G.D, k_copy_exit_face, dim3((unsigned)((cnt + WL_BLOCK - 1) / WL_BLOCK)), dim3(WL_BLOCK), 0, s, G, dst, src);
-  WL_LAUNCH_CHECK(); return 0;
-}
 int wl_sim::exit_bc(hipStream_t s) {
   if (comm) {   // z-slabs: the exit face is shared by all ranks — global means from per-rank sums (one 128-byte all-gather each)
     if (!exit_sc) WL_HIP(hipMalloc((void**)&exit_sc, 2 * sizeof(double)));
     WL_TRY(sync_u(s));
-    const long gcnt = (long)(G.ny - 2) * (G.gnz - 2), lcnt = (long)(G.ny - 2) * (G.k1 - G.k0);
-    const unsigned nbl = (unsigned)((lcnt + WL_BLOCK - 1) / WL_BLOCK);
+    double* sum = mg->ws.res_d + WL_RD_EXIT;
     for (int mode = 0; mode < 2; mode++) {
-      hipLaunchKernelGGL(k_exit_facesum_part<3>, dim3(1), dim3(1024), 0, s, G, (const float*)u, mg->ws.res_d + WL_RD_EXIT, mode);
+      WL_TRY(wl::exit_bc_slab_sum(G, u, sum, mode, s));
       WL_TRY(wl::combine_results(comm, mg->ws, s));
-      hipLaunchKernelGGL(k_exit_mean, dim3(1), dim3(1), 0, s, (const double*)(mg->ws.res_d + WL_RD_EXIT), exit_sc, gcnt, mode);
-      hipLaunchKernelGGL(k_exit_update_slab<3>, dim3(nbl), dim3(WL_BLOCK), 0, s, G, u, (const float*)u0, (const double*)exit_sc, dt.back(), mode);
+      WL_TRY(wl::exit_bc_slab_update(G, u, u0, sum, exit_sc, dt.back(), mode, s));
     }
-    WL_LAUNCH_CHECK();
     return wl::halo(comm, u, G, d.D, 2, s);      // the exit face changed after BC!'s exchange
   }
-  return exit_bc_single(G, u, u0, mg->ws.res_d + WL_RD_EXIT, dt.back(), s);
-}
-
-// exitBC!(u,u⁰,Δt) on a single domain (src/core.jl:226-233): inflow mean -> convective update of the exit face (mode 0), its mean -> flux correction (mode 1)
-int wl_sim::exit_bc_single(const GridX& G, float* u, const float* u0, double* sc, float dt, hipStream_t s) {
-  const long cnt = (long)(G.ny - 2) * (G.D == 3 ? (G.nz - 2) : 1);
-  const unsigned nb = (unsigned)((cnt + WL_BLOCK - 1) / WL_BLOCK);
-  for (int mode = 0; mode < 2; mode++) {
-    DSEL(G.D, k_exit_facesum, dim3(1), dim3(1024), 0, s, G, (const float*)u, sc, mode);
-    DSEL(G.D, k_exit_update, dim3(nb), dim3(WL_BLOCK), 0, s, G, u, u0, sc, dt, mode);
-  }
-  WL_LAUNCH_CHECK(); return 0;
+  return wl::exit_bc_single(G, u, u0, mg->ws.res_d + WL_RD_EXIT, dt.back(), s);
 }
 extern "C" {
-
-int wl_exit_bc(float* u, const float* u0, const wl_grid* g, float dt, void* st) {
-  WL_CHECK(wl_grid_ok(g), "bad wl_grid"); WL_CHECK(g->D == 2 || g->nz == g->gnz, "exitBC! needs the whole x-exit face on one rank");
-  WL_TRY(wl_ctx_ensure());
-  const GridX G = gx(*g); hipStream_t s = wl_stream(st);
-  return wl_sim::exit_bc_single(G, u, u0, wl_red_ws(wl_ctx().red).res_d + WL_RD_EXIT, dt, s);
-}
-int wl_L2_inside(const float* a, const wl_grid* g, double* out, void* st) {
-  WL_CHECK(wl_grid_ok(g), "bad wl_grid"); WL_TRY(wl_ctx_ensure());
-  const GridX G = gx(*g); hipStream_t s = wl_stream(st);
-  const RedWs ws = wl_red_ws(wl_ctx().red);
-  dim3 grid = wl_plane_grid(G, wl_red_slots(G, G.k1 - G.k0));
-  DSEL(G.D, k_l2_inside, grid, dim3(WL_BLOCK), 0, s, G, a, ws.pa);
-  hipLaunchKernelGGL(k_fin1, dim3(1), dim3(WL_BLOCK), 0, s, ws.pa, (int)grid.x, ws.res_d + WL_RD_SUM);
-  WL_LAUNCH_CHECK();
-  return wl::read_results(ws, out, wl_upto(WL_RD_SUM), nullptr, 0, s);
-}
 
 static int sim_create_common(wl_sim** out, const wl_sim_desc* desc, wl_comm* comm, wl_mg* adopt = nullptr) {
   WL_CHECK(out && desc, "null pointer"); WL_CHECK(desc->D == 2 || desc->D == 3, "D must be 2 or 3");
@@ -1107,13 +793,13 @@ int wl_sim_counter(wl_sim* s, const char* name, long* out) {
   if (n == "part_za") { *out = s->mg->lv[0].za; return 0; }
   if (n == "part_zb") { *out = s->mg->lv[0].zb; return 0; }
   if (n == "launches") { *out = s->n_step_launches; return 0; }                    // kernel launches of this handle's mom_step! calls so far
-  if (n == "probe_records") { *out = s->probe_n; return 0; }                       // probe records held / refused by a full buffer
-  if (n == "probe_dropped") { *out = s->n_probe_dropped; return 0; }
-  if (n == "force_records") { *out = s->force_n; return 0; }                       // force records held / refused by a full buffer / active tiles of the list in use
-  if (n == "force_dropped") { *out = s->n_force_dropped; return 0; }
-  if (n == "mean_updates") { *out = s->n_mean_updates; return 0; }                 // updates of the mean-flow observer since wl_sim_set_meanflow / its period (0: off)
-  if (n == "mean_every") { *out = s->mean_mode ? s->mean_every : 0; return 0; }
-  if (n == "force_tiles") { *out = s->force_on ? s->fband.n_active : s->fimm.n_active; return 0; }
+  if (n == "probe_records") { *out = s->obs.probes.n; return 0; }                       // probe records held / refused by a full buffer
+  if (n == "probe_dropped") { *out = s->obs.probes.dropped; return 0; }
+  if (n == "force_records") { *out = s->obs.forces.n; return 0; }                       // force records held / refused by a full buffer / active tiles of the list in use
+  if (n == "force_dropped") { *out = s->obs.forces.dropped; return 0; }
+  if (n == "mean_updates") { *out = s->obs.n_mean_updates; return 0; }                 // updates of the mean-flow observer since wl_sim_set_meanflow / its period (0: off)
+  if (n == "mean_every") { *out = s->obs.mean_mode ? s->obs.mean_every : 0; return 0; }
+  if (n == "force_tiles") { *out = s->obs.force_on ? s->obs.fband.n_active : s->obs.fimm.n_active; return 0; }
   wl_set_error("unknown counter " + n); return WL_EINVAL;
 }
 int wl_sim_set_forcing(wl_sim* s, const float* U1, const float* a0, const float* a1) {
@@ -1131,10 +817,6 @@ int wl_sim_set_sgs(wl_sim* s, int model, float Cs, float Delta) {
   }
   s->sgs_model = model; s->sgs_Cs = Cs; s->sgs_Delta = Delta;
   return 0;
-}
-int wl_accelerate(float* r, const wl_grid* g, const float* a, void* st) {
-  WL_CHECK(wl_grid_ok(g) && a, "bad argument"); WL_TRY(wl_ctx_ensure());
-  return wl::accelerate(r, gx(*g), a, wl_stream(st));
 }
 int wl_sim_mom_step(wl_sim* s, void* st) { return s->mom_step(wl_stream(st)); }
 int wl_sim_mom_steps(wl_sim* s, int n, void* st) {
@@ -1172,128 +854,51 @@ int wl_sim_apply_ic(wl_sim* s, int kind, void* st) {
   }
   WL_LAUNCH_CHECK(); return 0;
 }
-static int to_body_arg(int D, const wl_body* b, BodyArg* o) {
-  WL_CHECK(b && (b->kind == WL_BODY_SPHERE || b->kind == WL_BODY_PLANE), "wl_body.kind must be WL_BODY_SPHERE or WL_BODY_PLANE");
-  o->kind = b->kind; o->R = b->R;
-  float mm = 0.f;
-  for (int q = 0; q < 3; q++) { o->c[q] = q < D ? b->c[q] : 0.f; o->m[q] = q < D ? b->m[q] : 0.f; o->V[q] = q < D ? b->V[q] : 0.f; mm += o->m[q] * o->m[q]; }
-  WL_CHECK(mm > 0.f, "wl_body.m (axis mask / plane normal) is zero");
-  return 0;
-}
 static wl_body sphere_body(const float* c, float R) {
   wl_body b{}; b.kind = WL_BODY_SPHERE; b.R = R;
   for (int q = 0; q < 3; q++) { b.c[q] = c[q]; b.m[q] = 1.f; }
   return b;
 }
-// measure!(flow,body;ϵ) on the caller's arrays (without the halo exchange / update!(pois) of the composite)   src/Body.jl:28-51
-static int measure_fields(float* sigma, float* mu0, float* mu1, float* V, const GridX& G, const BodyArg& bd, float eps, int exitBC, unsigned perdir, hipStream_t q) {
-  const int D = G.D; const size_t nc = (size_t)G.cs;
-  WL_TRY(wl::fill(V, 0.f, nc * D, q)); WL_TRY(wl::fill(mu0, 1.f, nc * D, q)); WL_TRY(wl::fill(mu1, 0.f, nc * D * D, q));             // Body.jl:29
-  DSEL(D, k_measure_body, wl_plane_grid(G, G.k1 - G.k0), dim3(WL_BLOCK), 0, q, G, sigma, mu0, mu1, V, bd, eps);
-  WL_LAUNCH_CHECK();
-  const float zero[3] = {0, 0, 0};
-  WL_TRY(wl::bc_vec(mu0, G, zero, 0, perdir, q));                                                                                   // Body.jl:49
-  return wl::bc_vec(V, G, zero, exitBC, perdir, q);                                                                                 // Body.jl:50
+// measure!(sim) of the body program P: the fields, their halos, the masks, the force recorder's band, update!(pois)   src/Body.jl:28-51, WaterLily.jl:148
+static int sim_measure(wl_sim* s, const SetArg& P, float eps, void* st) {
+  hipStream_t q = wl_stream(st); const GridX& G = s->G; const int D = s->d.D;
+  WL_TRY(wl::bodyset_measure_fields(s->sigma, s->mu0, s->mu1, s->V, G, P, eps, s->d.exitBC, s->d.perdir_mask, q));
+  WL_TRY(wl::halo(s->comm, s->mu0, G, D, 2, q)); WL_TRY(wl::halo(s->comm, s->V, G, D, 2, q));
+  WL_TRY(s->refresh_body_mask(q));
+  WL_TRY(s->obs.body_changed(G, P, q));
+  return s->mg->update(q);
 }
-// which: 0 pressure_force(p) (src/Metrics.jl:116-133), 1 viscous_force(u,ν) (:140-154); Float64 partial sums, flow.f untouched.
-// On z-slabs every rank sums its own planes and the per-rank sums are added on device (one 128-byte all-gather).
-}  // extern "C"
-namespace wl {
-int force_reduce_with(const GridX& G, const RedWs& ws, wl_comm* comm, double* out, hipStream_t q, const std::function<int(dim3, double*, hipStream_t)>& partials) {
-  const int D = G.D;
-  dim3 grid = wl_plane_grid(G, wl_red_slots(G, G.k1 - G.k0));
-  // partials need 3*grid.x doubles (<= 3*WL_REDPART): pa and pb are contiguous (2*WL_MAXPART doubles)
-  WL_TRY(partials(grid, ws.pa, q));
-  hipLaunchKernelGGL(k_fin3, dim3(1), dim3(WL_BLOCK), 0, q, ws.pa, (int)grid.x, ws.res_d + WL_RD_FORCE);
-  WL_LAUNCH_CHECK();
-  WL_TRY(wl::combine_results(comm, ws, q));
-  std::lock_guard<std::mutex> lock(wl::wl_read_mutex());
-  WlCtx& cx = wl_ctx();
-  WL_HIP(hipMemcpyAsync(cx.h_d, ws.res_d + WL_RD_FORCE, 3 * sizeof(double), hipMemcpyDeviceToHost, q));
-  WL_HIP(hipStreamSynchronize(q));
-  for (int c = 0; c < D; c++) out[c] = cx.h_d[c];
-  return 0;
+// the handle's p (which = 0) or u (1) on the body program P; x0: the moment about that point.  Float64 partial sums, flow.f untouched; on z-slabs every rank
+// sums its own planes and the per-rank sums are added on device
+static int sim_force(int which, wl_sim* s, const float* x0, const SetArg& P, double* out, void* st) {
+  hipStream_t q = wl_stream(st);
+  WL_TRY(s->settle(q));                              // (∂u/∂z at the slab faces reads the neighbours' planes)
+  const float* a = which == 0 ? s->p : s->u; const float nu = which == 0 ? 0.f : s->d.nu; const GridX& G = s->G;
+  return wl::force_reduce_with(G, s->mg->ws, s->comm, out, q,
+                               [&](dim3 grid, double* part, hipStream_t qq) { return wl::bodyset_force_partials(which, a, nu, G, P, x0, grid, part, qq); });
 }
-}  // namespace wl
-extern "C" {
-static int force_reduce(int which, const float* a, float nu, const GridX& G, const BodyArg& bd, const RedWs& ws, wl_comm* comm, double* out, hipStream_t q, const float* x0 = nullptr) {
-  const int D = G.D;
-  MomArg mo{}; if (x0) { mo.on = 1; for (int c = 0; c < D; c++) mo.x0[c] = x0[c]; }
-  return wl::force_reduce_with(G, ws, comm, out, q, [&](dim3 grid, double* part, hipStream_t s) -> int {
-    if (which == 0) { DSEL(D, k_pforce_body, grid, dim3(WL_BLOCK), 0, s, G, a, bd, mo, part); }
-    else { DSEL(D, k_vforce_body, grid, dim3(WL_BLOCK), 0, s, G, a, nu, bd, mo, part); }
-    return 0;
-  });
-}
-int wl_measure_body(float* sigma, float* mu0, float* mu1, float* V, const wl_grid* g, const wl_body* body, float eps, int exitBC, uint32_t perdir_mask, void* st) {
-  WL_CHECK(wl_grid_ok(g), "bad wl_grid"); WL_CHECK(sigma && mu0 && mu1 && V, "null field");
-  BodyArg bd; WL_TRY(to_body_arg(g->D, body, &bd));
-  return measure_fields(sigma, mu0, mu1, V, gx(*g), bd, eps, exitBC, perdir_mask, wl_stream(st));
-}
-int wl_pressure_force_body(const float* p, const wl_grid* g, const wl_body* body, double* out, void* st) {
-  WL_CHECK(wl_grid_ok(g), "bad wl_grid"); WL_TRY(wl_ctx_ensure());
-  BodyArg bd; WL_TRY(to_body_arg(g->D, body, &bd));
-  return force_reduce(0, p, 0.f, gx(*g), bd, wl_red_ws(wl_ctx().red), nullptr, out, wl_stream(st));
-}
-int wl_viscous_force_body(const float* u, const wl_grid* g, float nu, const wl_body* body, double* out, void* st) {
-  WL_CHECK(wl_grid_ok(g), "bad wl_grid"); WL_TRY(wl_ctx_ensure());
-  BodyArg bd; WL_TRY(to_body_arg(g->D, body, &bd));
-  return force_reduce(1, u, nu, gx(*g), bd, wl_red_ws(wl_ctx().red), nullptr, out, wl_stream(st));
-}
-int wl_pressure_moment_body(const float* x0, const float* p, const wl_grid* g, const wl_body* body, double* out, void* st) {
-  WL_CHECK(wl_grid_ok(g) && x0, "bad wl_grid / x0"); WL_TRY(wl_ctx_ensure());
-  BodyArg bd; WL_TRY(to_body_arg(g->D, body, &bd));
-  return force_reduce(0, p, 0.f, gx(*g), bd, wl_red_ws(wl_ctx().red), nullptr, out, wl_stream(st), x0);
-}
-int wl_viscous_moment_body(const float* x0, const float* u, const wl_grid* g, float nu, const wl_body* body, double* out, void* st) {
-  WL_CHECK(wl_grid_ok(g) && x0, "bad wl_grid / x0"); WL_TRY(wl_ctx_ensure());
-  BodyArg bd; WL_TRY(to_body_arg(g->D, body, &bd));
-  return force_reduce(1, u, nu, gx(*g), bd, wl_red_ws(wl_ctx().red), nullptr, out, wl_stream(st), x0);
-}
-// the handle's p (which = 0) or u (1) on the body; x0: the moment about that point
 static int sim_force_body(int which, wl_sim* s, const float* x0, const wl_body* body, double* out, void* st) {
-  BodyArg bd; WL_TRY(to_body_arg(s->d.D, body, &bd));
-  WL_TRY(s->settle(wl_stream(st)));                  // (∂u/∂z at the slab faces reads the neighbours' planes)
-  return force_reduce(which, which == 0 ? s->p : s->u, which == 0 ? 0.f : s->d.nu, s->G, bd, s->mg->ws, s->comm, out, wl_stream(st), x0);
+  SetArg P; WL_TRY(wl::bodyset_from_body(s->d.D, body, &P));
+  return sim_force(which, s, x0, P, out, st);
 }
 int wl_sim_pressure_moment_body(wl_sim* s, const float* x0, const wl_body* body, double* out, void* st) { WL_CHECK(x0, "null x0"); return sim_force_body(0, s, x0, body, out, st); }
 int wl_sim_viscous_moment_body(wl_sim* s, const float* x0, const wl_body* body, double* out, void* st) { WL_CHECK(x0, "null x0"); return sim_force_body(1, s, x0, body, out, st); }
 int wl_sim_measure_body(wl_sim* s, const wl_body* body, float eps, void* st) {
   WL_CHECK(s->d.has_body && s->mu1 && s->V, "simulation was created with has_body=0");
-  BodyArg bd; WL_TRY(to_body_arg(s->d.D, body, &bd));
-  hipStream_t q = wl_stream(st); const GridX& G = s->G; const int D = s->d.D;
-  WL_TRY(measure_fields(s->sigma, s->mu0, s->mu1, s->V, G, bd, eps, s->d.exitBC, s->d.perdir_mask, q));
-  WL_TRY(wl::halo(s->comm, s->mu0, G, D, 2, q)); WL_TRY(wl::halo(s->comm, s->V, G, D, 2, q));
-  WL_TRY(s->refresh_body_mask(q));
-  if (s->force_on) {      // the recorder's body is the one just measured: the one-leaf program of this wl_body
-    wl_bodyset one{}; one.n = 1; wl_body_node& nd = one.node[0];
-    nd.op = WL_OP_LEAF; nd.kind = body->kind; nd.R = body->R;
-    for (int c = 0; c < 3; c++) { nd.c[c] = body->c[c]; nd.m[c] = body->m[c]; }
-    SetArg P; WL_TRY(wl::bodyset_prepare(D, &one, &P));
-    WL_TRY(s->force_body_changed(P, q));
-  }
-  return s->mg->update(q);                                                                                                          // WaterLily.jl:148
+  SetArg P; WL_TRY(wl::bodyset_from_body(s->d.D, body, &P));
+  return sim_measure(s, P, eps, st);
 }
 int wl_sim_pressure_force_body(wl_sim* s, const wl_body* body, double* out, void* st) { return sim_force_body(0, s, nullptr, body, out, st); }
 int wl_sim_viscous_force_body(wl_sim* s, const wl_body* body, double* out, void* st) { return sim_force_body(1, s, nullptr, body, out, st); }
 int wl_sim_measure_bodyset(wl_sim* s, const wl_bodyset* set, float eps, void* st) {
   WL_CHECK(s, "null wl_sim"); WL_CHECK(s->d.has_body && s->mu1 && s->V, "simulation was created with has_body=0");
   SetArg P; WL_TRY(wl::bodyset_prepare(s->d.D, set, &P));
-  hipStream_t q = wl_stream(st); const GridX& G = s->G; const int D = s->d.D;
-  WL_TRY(wl::bodyset_measure_fields(s->sigma, s->mu0, s->mu1, s->V, G, P, eps, s->d.exitBC, s->d.perdir_mask, q));
-  WL_TRY(wl::halo(s->comm, s->mu0, G, D, 2, q)); WL_TRY(wl::halo(s->comm, s->V, G, D, 2, q));
-  WL_TRY(s->refresh_body_mask(q));
-  WL_TRY(s->force_body_changed(P, q));
-  return s->mg->update(q);                                                                                                          // WaterLily.jl:148
+  return sim_measure(s, P, eps, st);
 }
 static int sim_force_bodyset(int which, wl_sim* s, const float* x0, const wl_bodyset* set, double* out, void* st) {
   WL_CHECK(s && out, "null wl_sim / out");
   SetArg P; WL_TRY(wl::bodyset_prepare(s->d.D, set, &P));
-  hipStream_t q = wl_stream(st);
-  WL_TRY(s->settle(q));                              // (∂u/∂z at the slab faces reads the neighbours' planes)
-  const float* a = which == 0 ? s->p : s->u; const float nu = which == 0 ? 0.f : s->d.nu; const GridX& G = s->G;
-  return wl::force_reduce_with(G, s->mg->ws, s->comm, out, q,
-                               [&](dim3 grid, double* part, hipStream_t qq) { return wl::bodyset_force_partials(which, a, nu, G, P, x0, grid, part, qq); });
+  return sim_force(which, s, x0, P, out, st);
 }
 int wl_sim_pressure_force_bodyset(wl_sim* s, const float* x0, const wl_bodyset* set, double* out, void* st) { return sim_force_bodyset(0, s, x0, set, out, st); }
 int wl_sim_viscous_force_bodyset(wl_sim* s, const float* x0, const wl_bodyset* set, double* out, void* st) { return sim_force_bodyset(1, s, x0, set, out, st); }
@@ -1334,27 +939,11 @@ int wl_sim_set_probes(wl_sim* s, const float* host_x, int m, int capacity) {
   WL_CHECK(s && m >= 0, "wl_sim_set_probes: null handle or negative m");
   if (s->comm) { wl_set_error("wl_sim_set_probes: z-slab handles are not supported (single domain only)"); return WL_EINVAL; }
   WL_CHECK(m == 0 || (host_x && capacity >= 1), "wl_sim_set_probes: null points or capacity < 1");
-  WL_HIP(hipDeviceSynchronize());      // records may still be in flight on the stream of the last step
-  s->free_probes(); s->n_probe_dropped = 0;
-  if (m == 0) return 0;
-  const size_t nx = (size_t)m * s->d.D, nr = (size_t)capacity * m * (s->d.D + 1);
-  WL_HIP(hipMalloc((void**)&s->probe_x, nx * sizeof(float)));
-  if (hipMalloc((void**)&s->probe_rec, nr * sizeof(float)) != hipSuccess) { s->free_probes(); wl_set_error("wl_sim_set_probes: hipMalloc failed for the record buffer"); return (int)hipErrorOutOfMemory; }
-  WL_HIP(hipMemcpy(s->probe_x, host_x, nx * sizeof(float), hipMemcpyHostToDevice));
-  s->probe_m = m; s->probe_cap = capacity;
-  return 0;
+  return s->obs.set_probes(s->d.D, host_x, m, capacity);
 }
 int wl_sim_read_probes(wl_sim* s, float* host_out, int cap_records, int* n_records, int* first_step) {
   WL_CHECK(s && n_records && first_step, "wl_sim_read_probes: null handle or result");
-  *n_records = s->probe_n; *first_step = (int)s->probe_first;
-  if (!host_out) return 0;             // a query: nothing is copied, the buffer keeps its records
-  WL_CHECK(cap_records >= s->probe_n, "wl_sim_read_probes: host_out takes fewer records than the buffer holds (nothing was read)");
-  if (s->probe_n) {
-    WL_HIP(hipMemcpyAsync(host_out, s->probe_rec, (size_t)s->probe_n * s->probe_m * (s->d.D + 1) * sizeof(float), hipMemcpyDeviceToHost, s->obs_stream));
-    WL_HIP(hipStreamSynchronize(s->obs_stream));
-  }
-  s->probe_n = 0;
-  return 0;
+  return s->obs.probes.read(host_out, cap_records, n_records, first_step, "wl_sim_read_probes");
 }
 static int force_handle_ok(wl_sim* s, const char* who) {
   WL_CHECK(s, "null wl_sim");
@@ -1366,27 +955,11 @@ int wl_sim_set_force_record(wl_sim* s, const wl_bodyset* host_set, const float* 
   WL_TRY(force_handle_ok(s, "wl_sim_set_force_record"));
   SetArg P;
   if (host_set) { WL_CHECK(capacity >= 1, "wl_sim_set_force_record: capacity < 1"); WL_TRY(wl::bodyset_prepare(s->d.D, host_set, &P)); }
-  WL_HIP(hipDeviceSynchronize());      // records may still be in flight on the stream of the last step
-  s->free_forces(); s->n_force_dropped = 0;
-  if (!host_set) return 0;
-  WL_HIP(hipMalloc((void**)&s->force_rec, (size_t)capacity * 12 * sizeof(double)));
-  for (int c = 0; c < 3; c++) s->force_x0[c] = (host_x0 && c < s->d.D) ? host_x0[c] : 0.f;
-  const int rc = s->fband.build(s->G, P, 0);
-  if (rc != 0) { s->free_forces(); return rc; }
-  s->force_cap = capacity; s->force_on = true;
-  return 0;
+  return s->obs.set_force_record(s->G, s->d.D, host_set ? &P : nullptr, host_x0, capacity);
 }
 int wl_sim_read_forces(wl_sim* s, double* host_out, int cap_records, int* n_records, int* first_step) {
   WL_CHECK(s && n_records && first_step, "wl_sim_read_forces: null handle or result");
-  *n_records = s->force_n; *first_step = (int)s->force_first;
-  if (!host_out) return 0;             // a query: nothing is copied, the buffer keeps its records
-  WL_CHECK(cap_records >= s->force_n, "wl_sim_read_forces: host_out takes fewer records than the buffer holds (nothing was read)");
-  if (s->force_n) {
-    WL_HIP(hipMemcpyAsync(host_out, s->force_rec, (size_t)s->force_n * 12 * sizeof(double), hipMemcpyDeviceToHost, s->force_stream));
-    WL_HIP(hipStreamSynchronize(s->force_stream));
-  }
-  s->force_n = 0;
-  return 0;
+  return s->obs.forces.read(host_out, cap_records, n_records, first_step, "wl_sim_read_forces");
 }
 int wl_sim_forces_bodyset(wl_sim* s, const float* host_x0, const wl_bodyset* host_set, double out[12], void* st) {
   WL_TRY(force_handle_ok(s, "wl_sim_forces_bodyset"));
@@ -1394,76 +967,56 @@ int wl_sim_forces_bodyset(wl_sim* s, const float* host_x0, const wl_bodyset* hos
   SetArg P; WL_TRY(wl::bodyset_prepare(s->d.D, host_set, &P));
   hipStream_t q = wl_stream(st);
   WL_TRY(s->settle(q));
-  WL_TRY(s->fimm.build(s->G, P, q));      // (a repeated call with the same body finds the list built: no launch, no read-back)
-  WL_TRY(s->fimm.run(s->G, s->p, s->u, s->d.nu, host_x0, s->fimm.out, q));
-  WL_HIP(hipMemcpyAsync(out, s->fimm.out, 12 * sizeof(double), hipMemcpyDeviceToHost, q));
-  WL_HIP(hipStreamSynchronize(q));
-  return 0;
+  return s->obs.forces_now(s->view(), P, host_x0, out, q);
 }
 int wl_sim_set_tracers(wl_sim* s, const float* host_x, size_t n) {
   WL_CHECK(s, "wl_sim_set_tracers: null handle");
   if (s->comm) { wl_set_error("wl_sim_set_tracers: z-slab handles are not supported (single domain only)"); return WL_EINVAL; }
   WL_CHECK(n == 0 || host_x, "wl_sim_set_tracers: null points");
-  WL_HIP(hipDeviceSynchronize());      // the last step's launch may still be moving the old swarm
-  s->free_tracers();
-  if (n == 0) return 0;
-  const size_t nb = n * (size_t)s->d.D * sizeof(float);
-  WL_HIP(hipMalloc((void**)&s->tr_x, nb));
-  if (hipMalloc((void**)&s->tr_x0, nb) != hipSuccess) { s->free_tracers(); wl_set_error("wl_sim_set_tracers: hipMalloc failed"); return (int)hipErrorOutOfMemory; }
-  WL_HIP(hipMemcpy(s->tr_x, host_x, nb, hipMemcpyHostToDevice));
-  WL_HIP(hipMemcpy(s->tr_x0, host_x, nb, hipMemcpyHostToDevice));      // position⁰ = position until the first step
-  s->tr_n = n;
-  return 0;
+  return s->obs.set_tracers(s->d.D, host_x, n);
 }
 static int mean_handle_ok(wl_sim* s, const char* who, int need_mode) {
   WL_CHECK(s, "null wl_sim");
   if (s->comm) { wl_set_error(std::string(who) + ": z-slab handles are not supported (single domain only)"); return WL_EINVAL; }
-  if (s->mean_mode < need_mode) { wl_set_error(std::string(who) + (need_mode == 2 ? ": the observer keeps no UU (wl_sim_set_meanflow mode 2)" : ": no mean-flow observer is set (wl_sim_set_meanflow)")); return WL_EINVAL; }
+  if (s->obs.mean_mode < need_mode) { wl_set_error(std::string(who) + (need_mode == 2 ? ": the observer keeps no UU (wl_sim_set_meanflow mode 2)" : ": no mean-flow observer is set (wl_sim_set_meanflow)")); return WL_EINVAL; }
   return 0;
 }
 int wl_sim_set_meanflow(wl_sim* s, int mode, int every, float t_init, void* st) {
   WL_TRY(mean_handle_ok(s, "wl_sim_set_meanflow", 0));
   WL_CHECK(mode >= 0 && mode <= 2, "wl_sim_set_meanflow: mode must be 0 (off), 1 (P, U) or 2 (P, U, UU)");
   WL_CHECK(mode == 0 || every >= 1, "wl_sim_set_meanflow: every < 1");
-  if (s->mean_own) WL_HIP(hipStreamSynchronize(s->mean_stream));      // an update may still be in flight on the stream of the last step
-  s->free_mean(); s->n_mean_updates = 0;
-  if (mode == 0) return 0;
-  if (hipMalloc((void**)&s->mean_own, s->mean_floats(mode) * sizeof(float)) != hipSuccess) { s->mean_own = nullptr; s->free_mean(); wl_set_error("wl_sim_set_meanflow: hipMalloc failed for the averages"); return (int)hipErrorOutOfMemory; }
-  s->mean_mode = mode; s->mean_every = every;
-  const int rc = s->mean_reset(std::isnan(t_init) ? (float)wl_sim_time(s) : t_init, wl_stream(st));
-  if (rc != 0) s->free_mean();
-  return rc;
+  return s->obs.set_meanflow(s->view(), mode, every, std::isnan(t_init) ? (float)wl_sim_time(s) : t_init, wl_stream(st));
 }
 int wl_sim_meanflow_reset(wl_sim* s, float t_init, void* st) {
   WL_TRY(mean_handle_ok(s, "wl_sim_meanflow_reset", 1));
-  return s->mean_reset(std::isnan(t_init) ? (float)wl_sim_time(s) : t_init, wl_stream(st));
+  return s->obs.mean_reset(std::isnan(t_init) ? (float)wl_sim_time(s) : t_init, wl_stream(st));
 }
 int wl_sim_meanflow_update(wl_sim* s, void* st) {
   WL_TRY(mean_handle_ok(s, "wl_sim_meanflow_update", 1));
   WL_TRY(s->settle(wl_stream(st)));      // (guards: between calls neither the divisor nor BC! is pending)
-  return s->mean_update(s->time_f(s->dt.size() - 1), wl_stream(st));
+  return s->obs.mean_update(s->view(), wl::Observers::time_f(s->dt, s->dt.size() - 1), wl_stream(st));
 }
 float* wl_sim_meanflow(wl_sim* s, int which, size_t* n) {
-  if (!s || !s->mean_mode || which < 0 || which > 2 || (which == 2 && s->mean_mode != 2)) return nullptr;
+  if (!s || !s->obs.mean_mode || which < 0 || which > 2 || (which == 2 && s->obs.mean_mode != 2)) return nullptr;
   const size_t cs = (size_t)s->G.cs;
   if (n) *n = cs * (size_t)(which == 0 ? 1 : which == 1 ? s->d.D : wl::meanflow_packed_planes(s->d.D));
-  return which == 0 ? s->mean_P() : which == 1 ? s->mean_U() : s->mean_UU();
+  return which == 0 ? s->obs.mean_P() : which == 1 ? s->obs.mean_U() : s->obs.mean_UU();
 }
 int wl_sim_meanflow_uu(wl_sim* s, float* out, int tau, void* st) {
   WL_TRY(mean_handle_ok(s, "wl_sim_meanflow_uu", 2));
   WL_CHECK(out, "wl_sim_meanflow_uu: null output");
-  return wl::meanflow_expand(out, s->mean_UU(), s->mean_U(), s->G, tau, wl_stream(st));
+  return wl::meanflow_expand(out, s->obs.mean_UU(), s->obs.mean_U(), s->G, tau, wl_stream(st));
 }
 int wl_sim_meanflow_t(const wl_sim* s, float* out, int cap) {
   if (!s) return 0;
-  const int n = (int)s->mean_t.size();
-  for (int k = 0; k < n && k < cap && out; k++) out[k] = s->mean_t[(size_t)k];
+  const int n = (int)s->obs.mean_t.size();
+  for (int k = 0; k < n && k < cap && out; k++) out[k] = s->obs.mean_t[(size_t)k];
   return n;
 }
 float* wl_sim_tracers(wl_sim* s, int which, size_t* n) {
   if (!s || (which != 0 && which != 1)) return nullptr;
-  if (n) *n = s->tr_n;
-  return which == 0 ? s->tr_x : s->tr_x0;
+  if (n) *n = s->obs.tr_n;
+  return which == 0 ? s->obs.tr_x : s->obs.tr_x0;
 }
 int wl_sim_viscous_force_sphere(wl_sim* s, const float* c, float R, double* out, void* st) { const wl_body b = sphere_body(c, R); return wl_sim_viscous_force_body(s, &b, out, st); }
 }  // extern "C"
