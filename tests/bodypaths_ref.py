@@ -1,7 +1,8 @@
 """NumPy restatement of what decides the body-aware fast paths (csrc/wl_flow.hip k_body_mask2, body_masks_box, body_masks_planes,
 conv_diff_bdim_body; csrc/wl_mg.hip wl_mg::update, wl_mg::zsplit_ranges): from host copies of μ₀, μ₁, V (ghost cells included, as FusedSimulation.field
 returns them) the three masks per (plane, workgroup of 256 consecutive in-plane cells), the two host scans, the census the library
-reports through wl_sim_counter("mask_*"), and the plane ranges the tiled conv_diff! and the z-split smoother take.  Test infrastructure."""
+reports through wl_sim_counter("mask_*"), and the plane ranges the tiled conv_diff! and the z-split smoother take.  Test infrastructure.
+tests/bodyshapes.py crosses this matrix with grid shapes: the gates of the body code that only a shape moves, and the z-split on coarse levels."""
 import numpy as np
 
 WG = 256          # WL_BLOCK: a workgroup is 256 consecutive cells m = i + j·nx of one plane (ghosts included), workgroup index m // 256
@@ -97,10 +98,11 @@ def tile_ranges(c, Ng, perdir=(), store_f=False):
 
 def zsplit_plan(mu0, perdir=()):
     """wl_mg::update on the finest level with the z-split's size gate at 0: (part, za, zb).  The constants are sampled at Julia cell (3,3,3);
-    planes za..zb hold a coefficient off the pattern; the split is taken when at least 16 planes and a quarter of all are 4 planes away."""
+    planes za..zb hold a coefficient off the pattern; the split is taken when the pair kernels take the level (even nx ≥ 34, ny ≥ 34, 8 planes) and at least 16
+    planes and a quarter of all are 4 planes away.  tests/bodyshapes.py zsplit_plan_level is the same on any level."""
     D = mu0.shape[-1]
     Ng = mu0.shape[:-1]
-    if D != 3 or perdir or Ng[0] < 34 or Ng[1] < 18 or Ng[2] - 2 < 8:
+    if D != 3 or perdir or Ng[0] < 34 or Ng[0] % 2 or Ng[1] < 34 or Ng[2] - 2 < 8:      # gsrb_fused_ok && gsrb_pair_geom_ok: even nx ≥ 34, ny ≥ 34, 8 planes
         return False, Ng[-1], -1
     c = mu0[2, 2, 2, :]
     pat = wall_pattern(Ng) * c

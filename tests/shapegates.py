@@ -7,7 +7,8 @@ inside it and the smallest just outside it (PAIRS; SHAPES is their union).  test
 oracle's hierarchy without a GPU; tests/test_gpu_shapegates.py runs every shape: default switches against optmatrix.PLAIN, bit for bit, and the dispatch the
 library reports against predicted().
 
-Out of scope, because other files own them: periodic directions, bodies and the z-split's own gates (tests/bodypaths_ref.py), 2-D, z-slabs."""
+Out of scope, because other files own them: periodic directions, the z-split's own gates and every gate a body adds (tests/bodyshapes.py, which crosses them
+with shapes; tests/bodypaths_ref.py), 2-D, z-slabs."""
 import callseq
 import optmatrix as om
 

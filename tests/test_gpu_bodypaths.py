@@ -44,9 +44,15 @@ def handle(w, case, opts, has_body=True):
     return sim
 
 
-def step(sim, fast, n=1):
-    """n × mom_step!; "body_tile" is a process-wide switch, so it is set for the handle that is about to run"""
+def step(sim, fast, n=1, convt_min=None, one_call=False):
+    """n × mom_step!; "body_tile" is a process-wide switch, so it is set for the handle that is about to run (and so is "convt_min", where the caller runs
+    handles with different size gates side by side); one_call: the n steps as one wl_sim_mom_steps"""
     sim.set_option("body_tile", 1 if fast else 0)
+    if convt_min is not None:
+        sim.set_option("convt_min", convt_min)
+    if one_call:
+        sim.mom_steps_(n)
+        return
     for _ in range(n):
         sim.mom_step_()
 
@@ -77,22 +83,48 @@ def steps_of(case, q):
     return [(body, 2)]
 
 
-def run_position(w, case, q, fast, plain):
-    """measure! + steps on both handles; on the fast handle the counters around the steps and the census against the restatement"""
+CONVT_MIN_DEFAULT = 2048      # wl_sim_create's conv_tile_min
+
+
+def run_position(w, case, q, fast, plain, default=None, each_call=False, steps3=False, check=None):
+    """measure! + steps on both handles; on the fast handle the counters around the steps and the census against the restatement.
+    default: a third handle with nothing set, held to plain as well (no tiled far range and no split level under its size gates, hybrid all the same);
+    each_call: one call per step with the states compared after every call instead of after the position; steps3: one wl_sim_mom_steps(3) on top;
+    check(what, fast, default, ref, fields, tr, kinds, n): the caller's own assertions in place of bp.CONDS (tests/test_gpu_bodyshapes.py)"""
     Ng = tuple(n + 2 for n in case["dims"])
     what = (case["id"], q)
+    names = ("u", "u0", "p", "f") if case["store_f"] else ("u", "u0", "p")
     for body, n in steps_of(case, q):
         if case["remeasure_each_step"] and body is not None:
             body = bp.moving_position(body, float(np.sum(fast.dt[:-1], dtype=np.float64)))
+        calls = ([(1, False)] * n if each_call else [(n, False)]) + ([(3, True)] if steps3 else [])
+        n = sum(k for k, _ in calls)
         measure(plain, body)
-        step(plain, False, n)
+        if not each_call:
+            step(plain, False, n)
         measure(fast, body)
         assert fast.counter("mask_valid") == 1, what
         dev = {k: fast.counter(k) for k in bp.CENSUS_NAMES}
         kinds, part = fast.smoother_kinds(), fast.counter("part")
-        h0, t0 = fast.counter("hybrid"), fast.counter("body_tile")
-        step(fast, True, n)
-        dh, dt_ = fast.counter("hybrid") - h0, fast.counter("body_tile") - t0
+        if default is not None:
+            measure(default, body)
+            assert {k: default.counter(k) for k in bp.CENSUS_NAMES} == dev and default.counter("part") == 0, what
+            hd = default.counter("hybrid")
+        dh = dt_ = 0
+        for i, (k, one) in enumerate(calls):
+            if each_call:
+                step(plain, False, k, one_call=one)
+            h0, t0 = fast.counter("hybrid"), fast.counter("body_tile")
+            step(fast, True, k, convt_min=0 if default is not None else None, one_call=one)
+            dh, dt_ = dh + fast.counter("hybrid") - h0, dt_ + fast.counter("body_tile") - t0
+            if default is not None:
+                t0 = default.counter("body_tile")
+                step(default, True, k, convt_min=CONVT_MIN_DEFAULT, one_call=one)
+                assert default.counter("body_tile") == t0, (what, i)
+            if each_call:
+                assert_same_state(fast, plain, what + ("call", i), names)
+                if default is not None:
+                    assert_same_state(default, plain, what + ("default", "call", i), names)
         # (read after the steps: handing out V or μ₁ invalidates the masks until the next measure!/update!)
         mu0, mu1, V = fast.field("mu0"), fast.field("mu1"), fast.field("V")
         assert fast.counter("mask_valid") == 0, what
@@ -102,15 +134,22 @@ def run_position(w, case, q, fast, plain):
         assert dev == {k: ref[k] for k in bp.CENSUS_NAMES}, (what, dev, ref)
         tr = bp.tile_ranges(ref, Ng, case["perdir"], case["store_f"])
         zp = bp.zsplit_plan(mu0, case["perdir"])
-        for name in case["positions"][q][1]:                    # the class this geometry is here for, on the device's own fields
-            assert bp.CONDS[name](ref, Ng, tr, zp), (what, name, ref, tr, zp)
+        if check is not None:
+            check(what, fast, default, ref, (mu0, mu1, V), tr, kinds, n)
+        else:
+            for name in case["positions"][q][1]:                    # the class this geometry is here for, on the device's own fields
+                assert bp.CONDS[name](ref, Ng, tr, zp), (what, name, ref, tr, zp)
         assert dh == (0 if case["exitBC"] else 2 * n), (what, dh)              # the convective exit: hybrid stands down, farmask stays
         assert dt_ == (0 if case["exitBC"] else tr[2] * 2 * n), (what, dt_, tr)
         assert part == int(zp[0]) and (kinds[0] == 3) == zp[0], (what, kinds, part, zp)
         if zp[0]:
             assert (fast.counter("part_za"), fast.counter("part_zb")) == zp[1:], (what, zp)
         assert plain.counter("hybrid") == 0 and plain.smoother_kinds()[0] != 3, what
-    assert_same_state(fast, plain, what, ("u", "u0", "p", "f") if case["store_f"] else ("u", "u0", "p"))
+        if default is not None:
+            assert default.counter("hybrid") - hd == (0 if case["exitBC"] else 2 * n) and 3 not in default.smoother_kinds(), what
+    assert_same_state(fast, plain, what, names)
+    if default is not None:
+        assert_same_state(default, plain, what + ("default",), names)
     return ref
 
 
