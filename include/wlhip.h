@@ -388,7 +388,8 @@ float* wl_sim_tracers(wl_sim* s, int which /*0 position, 1 position⁰*/, size_t
  * Leaf kinds are those of wl_body plus WL_BODY_CAPSULE: sdf = |ξ−p|−R, p the point of the segment c ± h·m (m the body-frame axis,
  * normalised by the library, h ≥ 0) closest to ξ — the flat plate of WaterLily cases.  A leaf with mapped=1 is evaluated at the
  * body-frame point ξ = R̂(x−x₀−xₚ)+xₚ of its rigid map; n = R̂ᵀg/|R̂ᵀg|, d = sdf/|R̂ᵀg|, velocity V + ω×(x−x₀−xₚ) (2-D: ω = w[0],
- * ω×b = ω(−b₂,b₁)) (src/AutoBody.jl:29-37).  An unmapped leaf measures exactly as wl_body does, with V = 0.
+ * ω×b = ω(−b₂,b₁)) (src/AutoBody.jl:29-37).  An unmapped leaf measures exactly as wl_body does, with V = 0.  A fourth kind, WL_BODY_LATTICE, takes its
+ * distance from sampled data instead of a formula: see "sampled bodies" below for its fields, its out-of-range rule and the lifetime of what it names.
  * UNION takes the smaller (d,n,V) tuple in Julia's isless order (min), INTERSECT the larger (max), NEGATE gives (−d,−n,V); a − b is
  * a ∩ (−b).  σ holds the raw sdf of a single-leaf program and measure(body,x;fastd²=(2+ϵ)²)[1] otherwise (src/Body.jl:67,74).
  * Malformed programs return WL_EINVAL before anything is launched. */
@@ -409,6 +410,43 @@ int wl_viscous_force_bodyset(const float* host_x0, const float* u, const wl_grid
 int wl_sim_measure_bodyset(wl_sim* s, const wl_bodyset* host_set, float eps, void* stream);       /* measure! + halos + update!(pois), as wl_sim_measure_body */
 int wl_sim_pressure_force_bodyset(wl_sim* s, const float* host_x0, const wl_bodyset* host_set, double out[3], void* stream);   /* collective on z-slabs */
 int wl_sim_viscous_force_bodyset(wl_sim* s, const float* host_x0, const wl_bodyset* host_set, double out[3], void* stream);
+
+/* ---- sampled bodies: a leaf whose distance comes from data (src/Body.jl:74 measure_sdf!, src/util.jl:17-43 interp, src/AutoBody.jl:29-37) -------
+ * A wl_sdf_lattice is what measure_sdf!(a, body) leaves in a scalar array: distances, in flow-grid cells, sampled at the cell centres loc(0,I) = I − 1.5 of
+ * its own grid, one ghost layer included — sample i (0-based) of a direction sits at lattice coordinate i − ½.  The leaf WL_BODY_LATTICE is the body
+ *     AutoBody((ξ,t) -> interp((ξ .- c) ./ s, A) - R, map)            map: the node's rigid map (mapped = 1) or the identity
+ * measured by measure(::AutoBody, x, t; fastd²).  Fields of a wl_body_node of this kind:
+ *     c     body-frame position of lattice coordinate 0 (sample i then sits at c + s·(i − ½))
+ *     m[0]  s > 0: flow-grid cells per sample interval (m[1], m[2] are ignored).  Distances are NOT rescaled: A holds flow-grid cells whatever s is
+ *     R     offset subtracted from the sampled value (R > 0 grows the body)
+ *     h     the lattice id, wl_sdf_lattice_id, stored as a float (ids are small positive integers: exactly representable)
+ * Value: d = interp(q, A) − R with q = (ξ − c)/s: interp's statements as wl_interp follows them — clamp of q to [0, n_d − 2], + 1.5, floor, the 2^D corners in
+ * CartesianIndices order, each weight the product over d left to right, Float32, nothing contracted.  d² > fastd² returns n = V = 0.  Otherwise the gradient
+ * is what ForwardDiff gives through _interp: g_d = (Σ_J A[J]·(±1)_d·Π_{e≠d} w_e(J))/s over the same corners in the same order, with i = floor(x) held fixed
+ * (the cell to the right of a node is used) and g_d = 0 where the clamp moves q_d; then, as for every leaf, the NaN test, n = R̂ᵀg, m = |n|, d /= m, n /= m
+ * and V + ω×(x−x₀−xₚ).  This is the one leaf with m ≠ 1 away from a coordinate scaling.  A lattice leaf composes under UNION / INTERSECT / NEGATE like any other.
+ *
+ * Out of range is defined: the clamp keeps every index inside the array, so no address outside the lattice is ever formed; a point outside the box
+ * q ∈ [0, n_d − 2] reads the value at the nearest point of the box and a zero gradient in the clamped directions.  Such a point must take the early exit, so
+ * wl_sdf_lattice_create records edge_min = min |A| over the samples a clamped query reads — the two outermost layers of every direction, between which the
+ * faces of the box interpolate — (0 if they differ in sign), and with it |d| ≥ edge_min − |R| outside the box.  Calls that measure fields (wl_measure_bodyset,
+ * wl_sim_measure_bodyset) return WL_EINVAL before any launch unless edge_min − |R| > 2 + ϵ + 1 for every lattice leaf; the force calls (wl_*_force_bodyset,
+ * wl_sim_*_force_bodyset, wl_sim_forces_bodyset, wl_sim_set_force_record), whose fastd² is 1, unless edge_min − |R| > 2.  wl_bodyset_measure_points applies no
+ * rule: it takes the caller's fastd² and returns the clamped value.
+ *
+ * Lifetime: at most 8 lattices are alive in a process; ids start at 1 and are never reused.  A program that names an unknown or destroyed id is refused with
+ * WL_EINVAL before anything is launched.  Programs the library keeps — the force recorder's and that of the last wl_sim_forces_bodyset — are looked up again by
+ * id before every launch that uses them: after the lattice is destroyed, wl_sim_mom_step / wl_sim_mom_steps on a handle whose recorder names it return WL_EINVAL
+ * and launch nothing (set another recorder body, or switch it off, to go on).  wl_sdf_lattice_destroy waits for the device before it frees.
+ *
+ * wl_sdf_lattice_create copies host_values[dims[0]·…·dims[D−1]] (first index fastest, offsets 64-bit) to the device on its last argument, the stream (a
+ * hipStream_t as void*, NULL = default), and synchronises that stream: host_values are the caller's again when it returns.  Its stream-contract scenario
+ * is tests/test_gpu_streams_lattice.py.  WL_EINVAL, with the reason, for D ∉ {2,3}, an extent below 3, a sample that is not finite, and a ninth live lattice. */
+enum { WL_BODY_LATTICE = 4 };
+typedef struct wl_sdf_lattice wl_sdf_lattice;
+int wl_sdf_lattice_create(wl_sdf_lattice** out, int D, const int32_t* dims, const float* host_values, void* hip_stream);
+int wl_sdf_lattice_destroy(wl_sdf_lattice* lattice);          /* NULL: nothing to do */
+int wl_sdf_lattice_id(const wl_sdf_lattice* lattice);         /* 0 for NULL or a handle that is not alive */
 
 /* ---- force history: pressure/viscous force and moment of a body after every step, from the body's band only (src/Metrics.jl:116-195) --------
  * nds(body,x) is zero outside |d| ≤ 1, so the sums run over a list of ACTIVE TILES — boxes of 64×4×4 array cells (2-D: 64×4) with an interior cell at

@@ -1,6 +1,6 @@
 """Composite bodies — the device form of the reference's RigidMap (src/RigidMap.jl) and SetBody (src/Body.jl:91-107).
 
-A body is a tree of closed-form leaves, each optionally under a rigid map, combined with `|` (∪, min), `&` (∩, max), unary `-`
+A body is a tree of leaves — closed-form shapes, or a distance field sampled on a lattice (SdfLattice) — each optionally under a rigid map, combined with `|` (∪, min), `&` (∩, max), unary `-`
 and binary `-` (a ∩ (−b)).  `.program(D)` flattens it into the postfix wl_bodyset of include/wlhip.h; every measure!/force call
 validates the program on the host before anything is launched.
 
@@ -15,7 +15,8 @@ import numpy as np
 from ._lib import WL_BODYSET_MAX, WL_BODYSET_STACK, check, lib, wl_bodyset
 
 OP_LEAF, OP_UNION, OP_INTERSECT, OP_NEGATE = 0, 1, 2, 3
-SPHERE, PLANE, CAPSULE = 1, 2, 3
+SPHERE, PLANE, CAPSULE, LATTICE = 1, 2, 3, 4
+LATTICE_MAX = 8                                     # live lattices of a process (include/wlhip.h)
 f32 = np.float32
 
 
@@ -94,8 +95,9 @@ def _pad(v, n=3):
 
 
 class Body(AbstractBody):
-    """A closed-form leaf: ("sphere", c, R) | ("cylinder", c, R, axis) | ("plane", point, normal) | ("capsule", c, R, axis_vector, h),
-    optionally under a RigidMap (evaluated at ξ = map(x))."""
+    """A leaf: ("sphere", c, R) | ("cylinder", c, R, axis) | ("plane", point, normal) | ("capsule", c, R, axis_vector, h) |
+    ("lattice", SdfLattice, origin, spacing, offset) — sdf(ξ) = interp((ξ − origin)/spacing, A) − offset: sample i sits at origin + spacing·(i − ½),
+    the samples are distances in flow-grid cells whatever the spacing — optionally under a RigidMap (evaluated at ξ = map(x))."""
 
     def __init__(self, shape, map=None):
         self.shape, self.map = tuple(shape), map
@@ -114,6 +116,14 @@ class Body(AbstractBody):
             nd.kind, R, m = PLANE, 0.0, self.shape[2]
         elif name == "capsule":
             nd.kind, R, m, h = CAPSULE, self.shape[2], self.shape[3], self.shape[4]
+        elif name == "lattice":
+            lat, c, spacing = self.shape[1], self.shape[2], self.shape[3]
+            if lat.D != D:
+                raise ValueError(f"a {lat.D}-D lattice in a {D}-D body program")
+            if not float(spacing) > 0:
+                raise ValueError("lattice spacing must be > 0")
+            c = np.broadcast_to(np.asarray(c, dtype=f32), (D,))
+            nd.kind, R, m, h = LATTICE, (self.shape[4] if len(self.shape) > 4 else 0.0), [spacing], lat.id      # the id travels as a float: a small integer, exact
         else:
             raise ValueError(f"unknown body {name!r}")
         nd.c[:] = _pad(c)
@@ -135,6 +145,81 @@ class Body(AbstractBody):
         if self.map is None:
             raise ValueError("setmap: this leaf has no RigidMap")
         return Body(self.shape, self.map.replace(**kw))
+
+
+class SdfLattice:
+    """A sampled distance field on the device (wl_sdf_lattice of include/wlhip.h): what measure_sdf!(a, body) leaves in a scalar array — distances in
+    flow-grid cells at the cell centres of the lattice's own grid, one ghost layer included.  Owns the handle: close() — or leaving a `with` block —
+    destroys it (waits for the device); a program that still names it is then refused.  At most LATTICE_MAX are alive in a process.
+
+        with SdfLattice(values) as lat:                       # values: (n_x, n_y[, n_z]) floats, every extent >= 3
+            hull = Body(("lattice", lat, origin, spacing, 0.0), map=RigidMap(x0, theta))
+    """
+
+    def __init__(self, values):
+        a = np.asarray(values, dtype=f32)
+        if a.ndim not in (2, 3):
+            raise ValueError("SdfLattice: values must be a 2-D or 3-D array")
+        self.D, self.dims = a.ndim, tuple(int(n) for n in a.shape)
+        self.edge_min = edge_min(a) if min(self.dims) >= 3 else 0.0
+        flat = np.ascontiguousarray(a.reshape(-1, order="F"))        # first index fastest, as every array of the library
+        h = C.c_void_p()
+        self._h = None
+        check(lib().wl_sdf_lattice_create(C.byref(h), self.D, (C.c_int32 * self.D)(*self.dims), flat.ctypes.data_as(C.POINTER(C.c_float)), None))
+        self._h = h
+        self.id = int(lib().wl_sdf_lattice_id(h))
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            check(lib().wl_sdf_lattice_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:      # interpreter shutdown: the library may be gone already
+            pass
+
+    @staticmethod
+    def centres(dims, origin=0, spacing=1):
+        """the positions of the samples of a lattice of `dims` samples: origin + spacing·(i − ½), as (prod(dims), D) Float32 rows, first index fastest"""
+        D = len(dims)
+        o = np.broadcast_to(np.asarray(origin, dtype=f32), (D,))
+        ax = [(o[q] + f32(spacing) * (np.arange(dims[q], dtype=f32) - f32(0.5))).astype(f32) for q in range(D)]
+        g = np.meshgrid(*ax, indexing="ij")
+        return np.stack([v.reshape(-1, order="F") for v in g], axis=1)
+
+    @classmethod
+    def bake(cls, body, dims, origin=0, spacing=1):
+        """sample an existing body program at the lattice's cell centres — measure_sdf!(a, body): d alone, fastd² = 0 — through the device's point probe;
+        Body(("lattice", bake(body, dims, origin, spacing), origin, spacing)) then stands where `body` stood"""
+        d, _, _ = measure(body, cls.centres(dims, origin, spacing), fastd2=0.0)
+        return cls(d.reshape(tuple(dims), order="F"))
+
+
+def edge_min(values):
+    """min |A| over the samples a clamped query reads — the two outermost layers of every direction — or 0 where they differ in sign (include/wlhip.h, out of
+    range): outside the lattice's box |sdf| >= edge_min − |offset|"""
+    a = np.asarray(values, dtype=f32)
+    edge = np.zeros(a.shape, dtype=bool)
+    for q in range(a.ndim):
+        ix = [slice(None)] * a.ndim
+        for sl in (slice(0, 2), slice(-2, None)):
+            ix[q] = sl
+            edge[tuple(ix)] = True
+    v = a[edge]
+    return 0.0 if (v > 0).any() and (v < 0).any() else float(np.abs(v).min())
+
+
+def lattice_margin_ok(body, D, need):
+    """the out-of-range rule of include/wlhip.h for `body`: every lattice leaf keeps edge_min − |offset| > need (2 + ϵ + 1 for measure!, 2 for the forces)"""
+    return all(f32(b.shape[1].edge_min) - abs(f32(b.shape[4] if len(b.shape) > 4 else 0.0)) > f32(need) for b in leaves(body) if b.shape[0] == "lattice")
 
 
 class SetBody(AbstractBody):

@@ -5,7 +5,9 @@
 // The program is a kernel argument (2 KB, kernarg memory): every node field is a scalar load and every branch on it is
 // wave-uniform.  The evaluation stack is per lane, at most WL_BODYSET_STACK entries of (d, n, V) in registers.
 #include <cmath>
+#include <cstring>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "wl_common.hpp"
@@ -30,7 +32,7 @@ __global__ void __launch_bounds__(WL_BLOCK) k_measure_set(GridX g, float* __rest
     float x[3]; for (int q = 0; q < 3; q++) x[q] = (float)I[q] - 1.5f;
     const float d2 = (2 + e) * (2 + e);
     float dc;
-    if (P.leaf_root) dc = leaf_sdf<D>(P.node[0], x);
+    if (P.leaf_root) dc = leaf_sdf<D>(P.node[0], P.lat, x);
     else { float nq[3], vq[3]; set_measure<D, S>(P, x, d2, dc, nq, vq); }
     sig[o] = dc;
     if (dc * dc < d2) {
@@ -138,11 +140,41 @@ __global__ void __launch_bounds__(WL_BLOCK) k_points_set(SetArg P, const float* 
 }  // namespace
 
 namespace wl {
+// a WL_BODY_LATTICE leaf (wlhip.h): c the position of lattice coordinate 0, m[0] = s, R the offset, h the id -> the prepared node, its lattice in out->lat[]
+static int prepare_lattice_leaf(int D, const wl_body_node& a, wl_body_node& b, SetArg* out) {
+  WL_CHECK(a.m[0] > 0.f && std::isfinite(a.m[0]), "wl_body_node.m[0] (grid cells per sample interval of a lattice leaf) must be > 0");
+  WL_CHECK(std::isfinite(a.R), "wl_body_node.R (offset of a lattice leaf) is not finite");
+  WL_CHECK(a.h >= 1.f && a.h < 16777216.f && a.h == std::floor(a.h), "wl_body_node.h of a lattice leaf must hold a lattice id (a positive integer)");
+  const int id = (int)a.h;
+  int32_t slot = 0;
+  while (slot < out->nlat && out->lat[slot].id != id) slot++;
+  LatRef L; float edge = 0.f;
+  WL_TRY(wl::lattice_resolve(id, D, &L, &edge));
+  if (slot == out->nlat) {
+    WL_CHECK(slot < WL_LATTICE_MAX, "wl_bodyset: more than WL_LATTICE_MAX lattices in one program");      // (guard: no more than that many are alive)
+    out->lat[slot] = L; out->nlat++;
+  }
+  out->lat_margin = std::fmin(out->lat_margin, edge - std::fabs(a.R));
+  b.m[0] = a.m[0]; b.m[1] = b.m[2] = 0.f;
+  static_assert(sizeof(slot) == sizeof(b.h), "the slot index travels as the bits of h");
+  std::memcpy(&b.h, &slot, sizeof(slot));
+  return 0;
+}
+int bodyset_resolve(int D, SetArg* P) {
+  for (int q = 0; q < P->nlat; q++) { float edge; WL_TRY(wl::lattice_resolve(P->lat[q].id, D, &P->lat[q], &edge)); }
+  return 0;
+}
+int bodyset_lattice_margin(const SetArg& P, float need, const char* who) {
+  if (P.nlat == 0 || P.lat_margin > need) return 0;
+  wl_set_error(std::string(who) + ": a lattice leaf's edge_min − |R| = " + std::to_string(P.lat_margin) + " is not above " + std::to_string(need) +
+               " — a cell outside the lattice's box could miss the early exit (wlhip.h, sampled bodies: out of range)");
+  return WL_EINVAL;
+}
 int bodyset_prepare(int D, const wl_bodyset* s, SetArg* out) {
   WL_CHECK(D == 2 || D == 3, "bad dimension");
   WL_CHECK(s, "null wl_bodyset");
   WL_CHECK(s->n >= 1 && s->n <= WL_BODYSET_MAX, "wl_bodyset.n must be 1..WL_BODYSET_MAX");
-  *out = SetArg{};
+  *out = SetArg{}; out->lat_margin = INFINITY;
   out->n = s->n;
   int sp = 0;
   for (int i = 0; i < s->n; i++) {
@@ -150,12 +182,15 @@ int bodyset_prepare(int D, const wl_bodyset* s, SetArg* out) {
     wl_body_node& b = out->node[i];
     b.op = a.op;
     if (a.op == WL_OP_LEAF) {
-      WL_CHECK(a.kind == WL_BODY_SPHERE || a.kind == WL_BODY_PLANE || a.kind == WL_BODY_CAPSULE, "wl_body_node.kind must be WL_BODY_SPHERE, WL_BODY_PLANE or WL_BODY_CAPSULE");
+      WL_CHECK(a.kind == WL_BODY_SPHERE || a.kind == WL_BODY_PLANE || a.kind == WL_BODY_CAPSULE || a.kind == WL_BODY_LATTICE,
+               "wl_body_node.kind must be WL_BODY_SPHERE, WL_BODY_PLANE, WL_BODY_CAPSULE or WL_BODY_LATTICE");
       b.kind = a.kind; b.R = a.R; b.h = a.h; b.mapped = a.mapped ? 1 : 0;
       float mm = 0.f;
       for (int q = 0; q < 3; q++) { b.c[q] = q < D ? a.c[q] : 0.f; b.m[q] = q < D ? a.m[q] : 0.f; mm += b.m[q] * b.m[q]; }
-      WL_CHECK(mm > 0.f, "wl_body_node.m (axis mask / normal / capsule axis) is zero");
-      if (a.kind == WL_BODY_CAPSULE) {
+      WL_CHECK(mm > 0.f || a.kind == WL_BODY_LATTICE, "wl_body_node.m (axis mask / normal / capsule axis) is zero");
+      if (a.kind == WL_BODY_LATTICE) {
+        WL_TRY(prepare_lattice_leaf(D, a, b, out));
+      } else if (a.kind == WL_BODY_CAPSULE) {
         WL_CHECK(a.h >= 0.f, "wl_body_node.h (capsule half-length) must be >= 0");
         const float l = sqrtf(mm);
         for (int q = 0; q < D; q++) b.m[q] = b.m[q] / l;
@@ -187,7 +222,7 @@ int bodyset_prepare(int D, const wl_bodyset* s, SetArg* out) {
 }
 int bodyset_from_body(int D, const wl_body* b, SetArg* out) {
   WL_CHECK(b && (b->kind == WL_BODY_SPHERE || b->kind == WL_BODY_PLANE), "wl_body.kind must be WL_BODY_SPHERE or WL_BODY_PLANE");
-  *out = SetArg{};
+  *out = SetArg{}; out->lat_margin = INFINITY;
   out->n = 1; out->leaf_root = 1; out->depth = 1;
   wl_body_node& nd = out->node[0];
   nd.op = WL_OP_LEAF; nd.kind = b->kind; nd.R = b->R;
@@ -200,6 +235,7 @@ int bodyset_from_body(int D, const wl_body* b, SetArg* out) {
   return 0;
 }
 int bodyset_measure_fields(float* sigma, float* mu0, float* mu1, float* V, const GridX& G, const SetArg& P, float eps, int exitBC, unsigned perdir, hipStream_t q) {
+  WL_TRY(bodyset_lattice_margin(P, 2.f + eps + 1.f, "measure!"));      // every interior cell and face outside a lattice's box takes the early exit at fastd² = (2+ϵ)²
   BSEL(G.D, P.depth, k_measure_set, wl_plane_grid(G, G.nz), dim3(WL_BLOCK), 0, q, G, sigma, mu0, mu1, V, P, eps);
   WL_LAUNCH_CHECK();
   const float zero[3] = {0, 0, 0};
@@ -207,9 +243,10 @@ int bodyset_measure_fields(float* sigma, float* mu0, float* mu1, float* V, const
   return wl::bc_vec(V, G, zero, exitBC, perdir, q);                                                                                 // Body.jl:50
 }
 int bodyset_force_partials(int which, const float* a, float nu, const GridX& G, const SetArg& P, const float* x0, dim3 grid, double* part, hipStream_t q) {
+  WL_TRY(bodyset_lattice_margin(P, 2.f, "force"));
   MomArg mo{}; if (x0) { mo.on = 1; for (int c = 0; c < G.D; c++) mo.x0[c] = x0[c]; }
   const wl_body_node& n0 = P.node[0];
-  if (which == 0 && P.leaf_root && !n0.mapped && n0.kind != WL_BODY_CAPSULE) {
+  if (which == 0 && P.leaf_root && !n0.mapped && (n0.kind == WL_BODY_SPHERE || n0.kind == WL_BODY_PLANE)) {
     if (G.D == 3) hipLaunchKernelGGL(k_pforce_body<3>, grid, dim3(WL_BLOCK), 0, q, G, a, body_arg(n0), mo, part);
     else hipLaunchKernelGGL(k_pforce_body<2>, grid, dim3(WL_BLOCK), 0, q, G, a, body_arg(n0), mo, part);
   } else if (which == 0) { BSEL(G.D, P.depth, k_pforce_set, grid, dim3(WL_BLOCK), 0, q, G, a, P, mo, part); }

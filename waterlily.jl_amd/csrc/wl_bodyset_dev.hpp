@@ -24,9 +24,10 @@ __device__ __forceinline__ void to_body_frame(const wl_body_node& nd, const floa
   for (int q = 0; q < D; q++) b[q] = (x[q] - nd.map.x0[q]) - nd.map.xp[q];
   for (int q = 0; q < D; q++) { float s = 0.f; for (int r = 0; r < D; r++) s += nd.map.R[q * 3 + r] * b[r]; xi[q] = s + nd.map.xp[q]; }
 }
-// closed-form sdf of a leaf at the body-frame point ξ (src/AutoBody.jl:21)
+// sdf of a leaf at the body-frame point ξ (src/AutoBody.jl:21): closed form, or sampled from lat[] for a lattice leaf (wl_lattice.hpp)
 template <int D>
-__device__ __forceinline__ float leaf_sdf_at(const wl_body_node& b, const float* xi) {
+__device__ __forceinline__ float leaf_sdf_at(const wl_body_node& b, const LatRef* lat, const float* xi) {
+  if (b.kind == WL_BODY_LATTICE) return lattice_sdf<D>(lat[__float_as_int(b.h)], b.c, b.m[0], b.R, xi);
   if (b.kind == WL_BODY_PLANE) { float s = 0.f; for (int q = 0; q < D; q++) s += b.m[q] * (xi[q] - b.c[q]); return s; }
   if (b.kind == WL_BODY_SPHERE) { float s = 0.f; for (int q = 0; q < D; q++) { const float dx = b.m[q] * (xi[q] - b.c[q]); s += dx * dx; } return sqrtf(s) - b.R; }
   float t = 0.f; for (int q = 0; q < D; q++) t += b.m[q] * (xi[q] - b.c[q]);
@@ -36,23 +37,23 @@ __device__ __forceinline__ float leaf_sdf_at(const wl_body_node& b, const float*
 }
 // raw sdf of a leaf at x: sdf(map(x)); an unmapped sphere/plane is body_sdf itself
 template <int D>
-__device__ __forceinline__ float leaf_sdf(const wl_body_node& b, const float* x) {
-  if (!b.mapped) return b.kind == WL_BODY_CAPSULE ? leaf_sdf_at<D>(b, x) : body_sdf<D>(body_arg(b), x);
+__device__ __forceinline__ float leaf_sdf(const wl_body_node& b, const LatRef* lat, const float* x) {
+  if (!b.mapped) return (b.kind == WL_BODY_SPHERE || b.kind == WL_BODY_PLANE) ? body_sdf<D>(body_arg(b), x) : leaf_sdf_at<D>(b, lat, x);
   float xi[3], bq[3];
   to_body_frame<D>(b, x, xi, bq);
-  return leaf_sdf_at<D>(b, xi);
+  return leaf_sdf_at<D>(b, lat, xi);
 }
 // measure(leaf,x;fastd²) -> d, n, V (n = V = 0 on the early exits)   src/AutoBody.jl:29-37
 template <int D>
-__device__ __forceinline__ void leaf_measure(const wl_body_node& b, const float* x, float fastd2, float& d, float* n, float* v) {
+__device__ __forceinline__ void leaf_measure(const wl_body_node& b, const LatRef* lat, const float* x, float fastd2, float& d, float* n, float* v) {
   for (int q = 0; q < 3; q++) { n[q] = 0.f; v[q] = 0.f; }
-  if (!b.mapped && b.kind != WL_BODY_CAPSULE) {          // the closed-form wl_body: V = its translation velocity (wl::bodyset_from_body; 0 in every public program)
+  if (!b.mapped && (b.kind == WL_BODY_SPHERE || b.kind == WL_BODY_PLANE)) {          // the closed-form wl_body: V = its translation velocity (wl::bodyset_from_body; 0 in every public program)
     if (body_measure<D>(body_arg(b), x, fastd2, d, n)) for (int q = 0; q < D; q++) v[q] = b.map.V[q];
     return;
   }
   float xi[3] = {x[0], x[1], x[2]}, bq[3] = {0.f, 0.f, 0.f};
   if (b.mapped) to_body_frame<D>(b, x, xi, bq);
-  d = leaf_sdf_at<D>(b, xi);
+  d = leaf_sdf_at<D>(b, lat, xi);
   if (d * d > fastd2) return;
   float g[3] = {0.f, 0.f, 0.f}; bool nan = false;
   if (b.kind == WL_BODY_PLANE) { for (int q = 0; q < D; q++) g[q] = b.m[q]; }
@@ -60,6 +61,8 @@ __device__ __forceinline__ void leaf_measure(const wl_body_node& b, const float*
     float s = 0.f; for (int q = 0; q < D; q++) { const float dx = b.m[q] * (xi[q] - b.c[q]); s += dx * dx; }
     const float rr = sqrtf(s);
     for (int q = 0; q < D; q++) g[q] = (b.m[q] * (xi[q] - b.c[q])) / rr;
+  } else if (b.kind == WL_BODY_LATTICE) {                  // the one leaf whose |∇sdf| is whatever the samples say: d /= m below does real work
+    lattice_grad<D>(lat[__float_as_int(b.h)], b.c, b.m[0], xi, g);
   } else {
     float t = 0.f; for (int q = 0; q < D; q++) t += b.m[q] * (xi[q] - b.c[q]);
     t = fminf(fmaxf(t, -b.h), b.h);
@@ -96,7 +99,7 @@ __device__ __forceinline__ void set_measure(const SetArg& P, const float* x, flo
     const wl_body_node& nd = P.node[i];
     if (nd.op == WL_OP_LEAF) {
       float dd, nq[3], vq[3];
-      leaf_measure<D>(nd, x, fastd2, dd, nq, vq);
+      leaf_measure<D>(nd, P.lat, x, fastd2, dd, nq, vq);
 #pragma unroll
       for (int s = 0; s < S; s++)
         if (s == sp) { st[s][0] = dd; for (int q = 0; q < D; q++) { st[s][1 + q] = nq[q]; st[s][1 + D + q] = vq[q]; } }

@@ -116,6 +116,7 @@ int ForceBand::tiles(const GridX& G, int* ntx, int* nty) {
 static TileGeom tile_geom(const GridX& G) { TileGeom t; (void)ForceBand::tiles(G, &t.ntx, &t.nty); t.nz_t = G.D == 3 ? WL_FT_Z : 1; return t; }
 
 int ForceBand::build(const GridX& G, const SetArg& prog, hipStream_t s) {
+  WL_TRY(bodyset_lattice_margin(prog, 2.f, "force band"));
   const long nt = tiles(G);
   WL_CHECK(nt >= 1 && nt < (1L << 30), "force band: tile count out of range");
   if (valid && n_tiles == (int)nt && std::memcmp(&P, &prog, sizeof(SetArg)) == 0) return 0;
@@ -146,8 +147,9 @@ int ForceBand::build(const GridX& G, const SetArg& prog, hipStream_t s) {
   valid = true;
   return 0;
 }
-int ForceBand::run(const GridX& G, const float* p, const float* u, float nu, const float* x0, double* dst, hipStream_t s) const {
+int ForceBand::run(const GridX& G, const float* p, const float* u, float nu, const float* x0, double* dst, hipStream_t s) {
   WL_CHECK(valid && p && u && dst, "force band: not built, or a null array");
+  WL_TRY(recheck(G.D));
   MomArg mo{}; mo.on = 1; for (int c = 0; c < G.D; c++) mo.x0[c] = x0 ? x0[c] : 0.f;
   if (n_active > 0) {      // (never a zero-sized launch)
     const TileGeom t = tile_geom(G);
@@ -157,6 +159,7 @@ int ForceBand::run(const GridX& G, const float* p, const float* u, float nu, con
   WL_LAUNCH_CHECK();
   return 0;
 }
+int ForceBand::recheck(int D) { return valid ? bodyset_resolve(D, &P) : 0; }
 void ForceBand::release() {
   if (flag) (void)hipFree(flag);
   if (out) (void)hipFree(out);

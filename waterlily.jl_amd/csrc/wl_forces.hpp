@@ -23,7 +23,9 @@ struct ForceBand {
   int build(const GridX& G, const SetArg& prog, hipStream_t s);
   // k_forces_band over the list + k_forces_fin: 12 doubles to dst (device) — pressure force, viscous force, pressure moment, viscous moment about x0,
   // three slots each.  An empty list launches the finish alone, which writes zeros.
-  int run(const GridX& G, const float* p, const float* u, float nu, const float* x0, double* dst, hipStream_t s) const;
+  // The stored program is resolved again first: WL_EINVAL, and no launch, when a lattice it names has been destroyed since the list was built.
+  int run(const GridX& G, const float* p, const float* u, float nu, const float* x0, double* dst, hipStream_t s);
+  int recheck(int D);      // that resolution alone (a time step with a recorder asks before it launches anything)
   void release();
 };
 }  // namespace wl

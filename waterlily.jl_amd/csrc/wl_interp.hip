@@ -2,10 +2,8 @@
 // one step of a tracer-particle swarm (the reference's pathline extension keeps `position`, `position⁰` and advances them once per
 // step with the current flow, ext/WaterLilyPathlinesExt.jl).
 //
-//   ip_one<D>      _interp(x, arr) :29-43 for one scalar array after _interp_clamp :17-18 — clamp, x += 1.5f, i = floor(x), y = x − i, then
-//                  the sum over the 2^D corners of CartesianIndices(I:I+1) in its own order (first dimension fastest), each weight the
-//                  product over d of (J_d == I_d ? 1−y_d : y_d) taken left to right, `s += arr[J]*weight` as a multiply and an add.
-//                  @fastmath @simd leaves the reference's association open; this is the written one (tests/interp_ref.py states the same).
+//   ip_one<D>      _interp(x, arr) :29-43 for one scalar array after _interp_clamp :17-18: ip_cell then ip_sum of wl_interp_dev.hpp, where the
+//                  statements and their order are written down (the lattice leaf of a body program samples through the same two)
 //   ip_vec<D>      interp(x, varr) :20-25 — component i is queried at x + ½·eᵢ (shift :23), then clamped like a scalar query (:24)
 //   k_interp<D>    one thread per point: the D coordinates are loaded once, then the vector array (D·2^D gathers) and/or the scalar array
 //                  (2^D gathers) is interpolated.  Outputs are point-major with a leading dimension each, so that wl_interp (n×ncomp),
@@ -15,6 +13,7 @@
 // the upper one is Ng_d − 1 at most.  It is written with fmaxf/fminf, which send a NaN coordinate to 0 (Julia's floor(Int, NaN) throws; a
 // kernel must not index with it).  All gathers use 64-bit offsets.  Nothing is contracted into FMAs.
 #include "wl_common.hpp"
+#include "wl_interp_dev.hpp"
 
 #pragma clang fp contract(off)
 
@@ -23,25 +22,9 @@ template <int D>
 __device__ __forceinline__ float ip_one(const float* __restrict__ a, const GridX& g, const float (&xq)[D]) {
   const int ng[3] = {g.nx, g.ny, g.nz};
   const long st[3] = {1, g.sy, g.sz};
-  float y[D]; long o = 0;
-#pragma unroll
-  for (int d = 0; d < D; d++) {
-    float c = fminf(fmaxf(xq[d], 0.f), (float)(ng[d] - 2));      // _interp_clamp :17-18
-    c += 1.5f;                                                   // x = x .+ 1.5f0 :31
-    const float fl = floorf(c);                                  // i = floor.(Int,x)
-    y[d] = c - fl;                                               // y = x.-i
-    o += (long)((int)fl - 1) * st[d];                            // Julia index i -> offset i − 1
-  }
-  float s = 0.f;                                                 // s = zero(T) :37
-#pragma unroll
-  for (int q = 0; q < (1 << D); q++) {                           // for J in I:I+oneunit(I) :38 — first dimension fastest
-    float w = (q & 1) ? y[0] : 1.f - y[0];                       // prod(@. ifelse(J.I==I.I,1-y,y)) :39
-    long oq = o + (q & 1);
-#pragma unroll
-    for (int d = 1; d < D; d++) { const int up = (q >> d) & 1; w = w * (up ? y[d] : 1.f - y[d]); oq += up ? st[d] : 0; }
-    s += a[oq] * w;                                              // s += arr[J]*weight :40
-  }
-  return s;
+  float y[D];
+  const long o = ip_cell<D>(ng, st, xq, y);
+  return ip_sum<D>(a, st, o, y);
 }
 // interp(x, varr) :20-25: out[i] = _interp(clamp(x + shift(i)), varr[..,i])
 template <int D>

@@ -1,0 +1,108 @@
+// Sampled distance fields (include/wlhip.h wl_sdf_lattice): what measure_sdf!(a, body) (src/Body.jl:74) leaves in a scalar array, copied to the device and
+// entered into a process-wide table of at most WL_LATTICE_MAX live lattices.  A body program names a lattice by its id; bodyset_prepare looks the id up here
+// and a stored program is looked up again before every launch, so a kernel only ever sees the pointer of a live lattice.  Host code only: the leaf's device
+// statements are in wl_lattice.hpp.
+#include <cmath>
+#include <mutex>
+#include <string>
+
+#include "wl_common.hpp"
+#include "wl_lattice.hpp"
+
+struct wl_sdf_lattice { int32_t id; int32_t D; int32_t n[3]; float* a; float edge_min; };
+
+namespace {
+std::mutex g_lat_mutex;
+wl_sdf_lattice* g_lat[WL_LATTICE_MAX] = {};
+int g_lat_next_id = 1;      // ids are never reused within a process
+
+// min|A| over the samples a query clamped in some direction reads — the two outermost layers of every direction — or 0 when they differ in sign: the value
+// outside the box is a convex combination of such samples, so with one sign its magnitude is at least this
+float edge_min_of(int D, const int32_t* n, const float* a) {
+  float lo = INFINITY; bool pos = false, neg = false;
+  const long nx = n[0], ny = n[1], nz = D == 3 ? n[2] : 1;
+  for (long k = 0; k < nz; k++)
+    for (long j = 0; j < ny; j++)
+      for (long i = 0; i < nx; i++) {
+        const bool edge = i < 2 || i >= nx - 2 || j < 2 || j >= ny - 2 || (D == 3 && (k < 2 || k >= nz - 2));
+        if (!edge) continue;
+        const float v = a[i + nx * (j + ny * k)];
+        lo = std::fmin(lo, std::fabs(v)); pos = pos || v > 0.f; neg = neg || v < 0.f;
+      }
+  return (pos && neg) ? 0.f : lo;
+}
+}  // namespace
+
+namespace wl {
+int lattice_resolve(int id, int D, LatRef* out, float* edge_min) {
+  std::lock_guard<std::mutex> lock(g_lat_mutex);
+  for (const wl_sdf_lattice* L : g_lat)
+    if (L && L->id == id) {
+      if (L->D != D) { wl_set_error("lattice " + std::to_string(id) + " has " + std::to_string(L->D) + " dimensions, the body program is evaluated in " + std::to_string(D)); return WL_EINVAL; }
+      out->a = L->a; out->id = id;
+      for (int q = 0; q < 3; q++) out->n[q] = L->n[q];
+      *edge_min = L->edge_min;
+      return 0;
+    }
+  wl_set_error("lattice id " + std::to_string(id) + " is unknown or has been destroyed (wl_sdf_lattice_create / _destroy)");
+  return WL_EINVAL;
+}
+}  // namespace wl
+
+extern "C" {
+int wl_sdf_lattice_create(wl_sdf_lattice** out, int D, const int32_t* dims, const float* host_values, void* st) {
+  WL_CHECK(out, "wl_sdf_lattice_create: null result"); *out = nullptr;
+  WL_CHECK(D == 2 || D == 3, "wl_sdf_lattice_create: D must be 2 or 3");
+  WL_CHECK(dims && host_values, "wl_sdf_lattice_create: null dims or values");
+  size_t count = 1;
+  for (int q = 0; q < D; q++) {
+    WL_CHECK(dims[q] >= 3, "wl_sdf_lattice_create: every extent must be at least 3 (one cell and its ghost layer)");
+    WL_CHECK(dims[q] <= (1 << 20), "wl_sdf_lattice_create: extent out of range");
+    count *= (size_t)dims[q];
+  }
+  for (size_t q = 0; q < count; q++)
+    if (!std::isfinite(host_values[q])) { wl_set_error("wl_sdf_lattice_create: sample " + std::to_string(q) + " is not finite"); return WL_EINVAL; }
+  std::lock_guard<std::mutex> lock(g_lat_mutex);
+  int slot = 0;
+  while (slot < WL_LATTICE_MAX && g_lat[slot]) slot++;
+  if (slot == WL_LATTICE_MAX) { wl_set_error("wl_sdf_lattice_create: WL_LATTICE_MAX (8) lattices are alive — destroy one first"); return WL_EINVAL; }
+  WL_TRY(wl_ctx_ensure());
+  wl_sdf_lattice* L = new wl_sdf_lattice{};
+  L->D = D;
+  for (int q = 0; q < 3; q++) L->n[q] = q < D ? dims[q] : 1;
+  L->edge_min = edge_min_of(D, L->n, host_values);
+  hipStream_t s = wl_stream(st);
+  hipError_t e = hipMalloc((void**)&L->a, count * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpyAsync(L->a, host_values, count * sizeof(float), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);      // the caller's host_values are free again, and every stream may read the samples, when this returns
+  if (e != hipSuccess) {
+    wl_set_error(std::string("wl_sdf_lattice_create: ") + hipGetErrorString(e));
+    if (L->a) (void)hipFree(L->a);
+    delete L;
+    return (int)e;
+  }
+  L->id = g_lat_next_id++;
+  g_lat[slot] = L;
+  *out = L;
+  return 0;
+}
+int wl_sdf_lattice_destroy(wl_sdf_lattice* L) {
+  if (!L) return 0;
+  std::lock_guard<std::mutex> lock(g_lat_mutex);
+  int slot = 0;
+  while (slot < WL_LATTICE_MAX && g_lat[slot] != L) slot++;
+  WL_CHECK(slot < WL_LATTICE_MAX, "wl_sdf_lattice_destroy: not a live lattice");
+  g_lat[slot] = nullptr;                    // from here on no program resolves it: nothing new can be launched on its samples
+  const hipError_t e = hipDeviceSynchronize();      // … and what was launched has finished before the memory goes
+  (void)hipFree(L->a);
+  delete L;
+  if (e != hipSuccess) { wl_set_error(std::string("wl_sdf_lattice_destroy: ") + hipGetErrorString(e)); return (int)e; }
+  return 0;
+}
+int wl_sdf_lattice_id(const wl_sdf_lattice* L) {
+  if (!L) return 0;
+  std::lock_guard<std::mutex> lock(g_lat_mutex);
+  for (const wl_sdf_lattice* q : g_lat) if (q == L) return L->id;
+  return 0;
+}
+}  // extern "C"

@@ -59,6 +59,8 @@ struct Observers {
   // ---- what the step asks
   // the probe or force record or the mean-flow update of the step now running reads p: its last projection tail has to store it ("pdefer")
   bool reads_p_after_this_step() const { return probe_m || force_on || mean_due(); }
+  // a step with a force recorder will launch the recorder's stored program: WL_EINVAL now, before anything runs, if a lattice it names has been destroyed
+  int before_step(int D) { return force_on ? fband.recheck(D) : 0; }
   int after_step(const StepView& v, hipStream_t s);      // probes, forces, tracers, mean — in this launch order; p is current (the caller sees to that)
   // measure!(sim) replaced the body: pressure_force(sim) always means sim.body as it is now, so the recorder follows it
   int body_changed(const GridX& G, const SetArg& P, hipStream_t s) { return force_on ? fband.build(G, P, s) : 0; }

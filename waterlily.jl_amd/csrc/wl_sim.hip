@@ -502,6 +502,7 @@ struct wl_sim {
     return obs.after_step(view(), s);
   }
   int mom_step(hipStream_t s, bool more_follow = false) {
+    WL_TRY(obs.before_step(d.D));
     const long l0 = g_wl_launches;
     const int rc = mom_step_body(s, more_follow);
     n_step_launches += g_wl_launches - l0;
@@ -872,6 +873,7 @@ static int sim_measure(wl_sim* s, const SetArg& P, float eps, void* st) {
 // sums its own planes and the per-rank sums are added on device
 static int sim_force(int which, wl_sim* s, const float* x0, const SetArg& P, double* out, void* st) {
   hipStream_t q = wl_stream(st);
+  WL_TRY(wl::bodyset_lattice_margin(P, 2.f, "force"));
   WL_TRY(s->settle(q));                              // (∂u/∂z at the slab faces reads the neighbours' planes)
   const float* a = which == 0 ? s->p : s->u; const float nu = which == 0 ? 0.f : s->d.nu; const GridX& G = s->G;
   return wl::force_reduce_with(G, s->mg->ws, s->comm, out, q,
@@ -954,7 +956,7 @@ static int force_handle_ok(wl_sim* s, const char* who) {
 int wl_sim_set_force_record(wl_sim* s, const wl_bodyset* host_set, const float* host_x0, int capacity) {
   WL_TRY(force_handle_ok(s, "wl_sim_set_force_record"));
   SetArg P;
-  if (host_set) { WL_CHECK(capacity >= 1, "wl_sim_set_force_record: capacity < 1"); WL_TRY(wl::bodyset_prepare(s->d.D, host_set, &P)); }
+  if (host_set) { WL_CHECK(capacity >= 1, "wl_sim_set_force_record: capacity < 1"); WL_TRY(wl::bodyset_prepare(s->d.D, host_set, &P)); WL_TRY(wl::bodyset_lattice_margin(P, 2.f, "wl_sim_set_force_record")); }
   return s->obs.set_force_record(s->G, s->d.D, host_set ? &P : nullptr, host_x0, capacity);
 }
 int wl_sim_read_forces(wl_sim* s, double* host_out, int cap_records, int* n_records, int* first_step) {
@@ -965,6 +967,7 @@ int wl_sim_forces_bodyset(wl_sim* s, const float* host_x0, const wl_bodyset* hos
   WL_TRY(force_handle_ok(s, "wl_sim_forces_bodyset"));
   WL_CHECK(out, "wl_sim_forces_bodyset: null result");
   SetArg P; WL_TRY(wl::bodyset_prepare(s->d.D, host_set, &P));
+  WL_TRY(wl::bodyset_lattice_margin(P, 2.f, "wl_sim_forces_bodyset"));
   hipStream_t q = wl_stream(st);
   WL_TRY(s->settle(q));
   return s->obs.forces_now(s->view(), P, host_x0, out, q);
