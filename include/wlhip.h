@@ -448,6 +448,38 @@ int wl_sdf_lattice_create(wl_sdf_lattice** out, int D, const int32_t* dims, cons
 int wl_sdf_lattice_destroy(wl_sdf_lattice* lattice);          /* NULL: nothing to do */
 int wl_sdf_lattice_id(const wl_sdf_lattice* lattice);         /* 0 for NULL or a handle that is not alive */
 
+/* ---- sampled bodies from meshes: the exact signed distance to a closed surface, sampled into a lattice on the device ----
+ * wl_sdf_lattice_from_mesh fills a lattice of dims[0..D) samples with the Euclidean distance to a closed surface given in the body frame, in flow-grid
+ * cells: D = 3 — nv vertices (x,y,z rows) and ne triangles as index triples; D = 2 — nv vertices (x,y rows) and ne segments as index pairs that form one
+ * or more closed polygons.  Sample i of direction d sits at origin_d + spacing·((float)i_d − 0.5f), the lattice leaf's own statement (c = origin, m[0] =
+ * spacing), so Body(("lattice", …, origin, spacing)) puts the surface where the vertices say.  Orientation is outward: counter-clockwise seen from the fluid,
+ * so that the signed volume (area) is positive.  The value is negative inside, positive outside, and d = 0 is stored as +0.
+ *
+ * Per (sample, element) the closest point is found by the region walk of Ericson (Real-Time Collision Detection §5.1.5: vertex A, B, C, edge AB, BC, CA,
+ * face; in 2-D vertex A, B, interior) in Float32, one written order, no contraction; a sample keeps the minimum of d² = |p − q|² over the elements in
+ * ascending index with a strict <, and with it the winner's region and p − q.  The sign is that of (p − q)·n with the angle-weighted pseudonormal of the
+ * winning feature (Bærentzen & Aanæs 2005: the face normal; the normalised sum of the two adjacent face normals on an edge; the normalised angle-weighted
+ * sum of the incident face normals at a vertex; in 2-D the edge normal and the normalised sum of the two adjacent unit edge normals), computed on the host
+ * in Float64 and rounded to Float32 once.  The search culls by bounding spheres per brick of 4×4×4 (4×16) samples and is exact: with flags = WL_MESH_BRUTE
+ * every pair is tested instead, and both forms store the same bits on every sample (csrc/wl_meshsdf.hip).
+ *
+ * The result is an ordinary lattice: the same table, the same limit of 8 alive, ids never reused, edge_min recorded from the samples as create records it
+ * (wl_sdf_lattice_edge_min; the out-of-range rule above applies unchanged — leave 5 + |R| cells of lattice around the surface).  The call works on
+ * hip_stream (uploads, one launch, the read-back) and synchronises it, like wl_sdf_lattice_create.  wl_sdf_lattice_read copies the samples of any live
+ * lattice to the host (first index fastest) on hip_stream and synchronises it; the scenario for both is tests/test_gpu_streams_meshsdf.py.
+ *
+ * WL_EINVAL with the reason, decided on the host before any launch or device allocation — the next valid call goes through — for: D ∉ {2,3}; an extent
+ * below 3; a spacing that is not finite or not positive; a non-finite origin or vertex; fewer than 4 vertices / 4 triangles (3 / 3 segments); an index
+ * outside [0, nv); a triangle of zero area or a segment of zero length; an edge that is not shared by exactly two triangles in opposite directions (open,
+ * non-manifold and inconsistently oriented surfaces, and unwelded triangle soup: weld coincident vertices first); in 2-D a vertex that does not have exactly
+ * one incoming and one outgoing segment; a signed volume / area that is not positive (oriented inward: reverse the index order); a ninth live lattice. */
+enum { WL_MESH_BRUTE = 1 };   /* flags: no culling */
+int   wl_sdf_lattice_from_mesh(wl_sdf_lattice** out, int D, const int32_t* dims, const float* host_origin, float spacing,
+                               const float* host_vertices, int32_t nv, const int32_t* host_elems, int32_t ne,
+                               unsigned flags, void* hip_stream);
+int   wl_sdf_lattice_read(const wl_sdf_lattice* lattice, float* host_values, void* hip_stream);  /* the samples, first index fastest; synchronises */
+float wl_sdf_lattice_edge_min(const wl_sdf_lattice* lattice);                                    /* what create recorded; 0 for NULL / not alive */
+
 /* ---- force history: pressure/viscous force and moment of a body after every step, from the body's band only (src/Metrics.jl:116-195) --------
  * nds(body,x) is zero outside |d| ≤ 1, so the sums run over a list of ACTIVE TILES — boxes of 64×4×4 array cells (2-D: 64×4) with an interior cell at
  * d² ≤ 1, found by evaluating the body program on every interior cell, in ascending order, rebuilt only when the body changes.  One launch with one

@@ -54,6 +54,9 @@ int wl_placement_scores(double* out, int cap);
  * (the recorder's, or without a recorder that of the last wl_sim_forces_bodyset);
  * "mean_updates" = updates of the mean-flow observer since wl_sim_set_meanflow (the observer's and wl_sim_meanflow_update's), "mean_every" = its period (0: off) */
 int wl_sim_counter(wl_sim* s, const char* name, long* out);
+/* the last wl_sdf_lattice_from_mesh of this process: exact (sample, element) closest-point tests made — the per-brick counts the kernel wrote, summed on the
+ * host — and samples × elements; equal under WL_MESH_BRUTE */
+int wl_meshsdf_last_pairs(uint64_t* tested, uint64_t* total);
 
 #ifdef __cplusplus
 }

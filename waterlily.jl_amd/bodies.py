@@ -169,6 +169,40 @@ class SdfLattice:
         self._h = h
         self.id = int(lib().wl_sdf_lattice_id(h))
 
+    @classmethod
+    def from_mesh(cls, vertices, elems, dims, origin=0, spacing=1, brute=False):
+        """the exact signed distance to a closed surface, sampled on the device (wl_sdf_lattice_from_mesh): `vertices` (nv × D) in the body frame, in flow-grid
+        cells; `elems` (ne × 3) triangles in 3-D, (ne × 2) segments of closed polygons in 2-D, oriented outward (counter-clockwise seen from the fluid);
+        sample i sits at origin + spacing·(i − ½), as for centres().  Negative inside.  brute=True tests every (sample, element) pair instead of culling: the
+        same bits, for tests and timings.  A mesh that is open, non-manifold, unwelded (see weld) or oriented inward raises WlError with the reason."""
+        v = np.ascontiguousarray(vertices, dtype=f32)
+        e = np.ascontiguousarray(elems, dtype=np.int32)
+        if v.ndim != 2 or v.shape[1] not in (2, 3) or e.ndim != 2 or e.shape[1] != v.shape[1]:
+            raise ValueError("from_mesh: vertices must be (nv, D) and elems (ne, D) — triangles in 3-D, segments in 2-D")
+        D = v.shape[1]
+        dims = tuple(int(n) for n in dims)
+        if len(dims) != D:
+            raise ValueError(f"from_mesh: {len(dims)} extents for a {D}-D mesh")
+        o = np.ascontiguousarray(np.broadcast_to(np.asarray(origin, dtype=f32), (D,)))
+        self = cls.__new__(cls)
+        self.D, self.dims, self._h = D, dims, None
+        h = C.c_void_p()
+        check(lib().wl_sdf_lattice_from_mesh(C.byref(h), D, (C.c_int32 * D)(*dims), o.ctypes.data_as(C.POINTER(C.c_float)), float(spacing),
+                                             v.ctypes.data_as(C.POINTER(C.c_float)), len(v), e.ctypes.data_as(C.POINTER(C.c_int32)), len(e),
+                                             1 if brute else 0, None))
+        self._h = h
+        self.id = int(lib().wl_sdf_lattice_id(h))
+        self.edge_min = float(lib().wl_sdf_lattice_edge_min(h))      # recorded by the library from the samples it made
+        return self
+
+    def values(self):
+        """the samples as an ndarray of shape `dims`, read back from the device (wl_sdf_lattice_read)"""
+        if self._h is None:
+            raise ValueError("SdfLattice.values: the lattice has been closed")
+        flat = np.empty(int(np.prod(self.dims)), dtype=f32)
+        check(lib().wl_sdf_lattice_read(self._h, flat.ctypes.data_as(C.POINTER(C.c_float)), None))
+        return flat.reshape(self.dims, order="F")
+
     def close(self):
         if self._h is not None:
             h, self._h = self._h, None
@@ -215,6 +249,53 @@ def edge_min(values):
             edge[tuple(ix)] = True
     v = a[edge]
     return 0.0 if (v > 0).any() and (v < 0).any() else float(np.abs(v).min())
+
+
+def mesh_placement(vertices, spacing=1.0, margin=5.0):
+    """the lattice mesh_body lays around the bounding box of `vertices`: (dims, origin) with origin_d = lo_d − margin − spacing/2 and
+    n_d = ceil((hi_d − lo_d + 2·margin)/spacing) + 3, so that samples 1 and n_d − 2 sit at least `margin` outside the box"""
+    v = np.asarray(vertices, dtype=np.float64)
+    lo, hi = v.min(axis=0), v.max(axis=0)
+    dims = tuple(int(np.ceil((hi[d] - lo[d] + 2.0 * margin) / spacing)) + 3 for d in range(v.shape[1]))
+    return dims, tuple(float(lo[d] - margin - spacing / 2.0) for d in range(v.shape[1]))
+
+
+def mesh_body(vertices, elems, spacing=1.0, margin=None, offset=0.0, map=None):
+    """A closed triangle mesh (2-D: closed polygons of segments) as a body: its exact signed distance sampled at `spacing` into a lattice around its
+    bounding box (SdfLattice.from_mesh, mesh_placement) and the lattice leaf over it — Body(("lattice", lat, origin, spacing, offset), map).  Vertices are
+    in the body frame, in flow-grid cells; `map` places and moves the body.  The lattice every sample of which lies `margin` or more outside the box has
+    edge_min ≥ margin; margin=None takes 5 + |offset|, which satisfies measure!'s rule edge_min − |offset| > 2 + ϵ + 1 at ϵ = 1 — a larger ϵ needs a
+    larger margin (ϵ + 4 + |offset|).  The lattice is the body's: body.shape[1].close() frees it (at most LATTICE_MAX are alive)."""
+    margin = 5.0 + abs(float(offset)) if margin is None else float(margin)
+    dims, origin = mesh_placement(vertices, float(spacing), margin)
+    lat = SdfLattice.from_mesh(vertices, elems, dims, origin, spacing)
+    return Body(("lattice", lat, origin, float(spacing), float(offset)), map)
+
+
+def weld(vertices, faces):
+    """merge exactly equal vertex rows and re-index: (vertices, faces) with every position named once, in order of first appearance — what a triangle soup
+    (an STL file) needs before from_mesh can tell which triangles share an edge"""
+    v = np.asarray(vertices)
+    f = np.asarray(faces)
+    # (−0.0 and +0.0 are the same position)
+    _, first, inverse = np.unique(v + v.dtype.type(0), axis=0, return_index=True, return_inverse=True)
+    order = np.argsort(first)                      # unique rows in order of first appearance
+    rank = np.empty_like(order); rank[order] = np.arange(len(order))
+    return v[first[order]], rank[np.asarray(inverse).reshape(-1)][f].astype(np.int32)
+
+
+def read_stl(path):
+    """a binary STL file as welded (vertices (nv × 3) Float32, faces (ne × 3) int32); the file's normals are ignored (the index order orients a triangle).
+    An ASCII STL raises ValueError."""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    n = int(np.frombuffer(raw[80:84], dtype="<u4")[0]) if len(raw) >= 84 else -1
+    if n < 0 or len(raw) != 84 + 50 * n:
+        if raw[:5].lower() == b"solid":
+            raise ValueError(f"{path}: an ASCII STL file — only binary STL is read (convert it first)")
+        raise ValueError(f"{path}: not a binary STL file ({len(raw)} bytes, header says {n} triangles)")
+    rec = np.frombuffer(raw, dtype=np.dtype([("n", "<f4", 3), ("v", "<f4", (3, 3)), ("a", "<u2")]), count=n, offset=84)
+    return weld(rec["v"].reshape(-1, 3).astype(f32), np.arange(3 * n, dtype=np.int32).reshape(n, 3))
 
 
 def lattice_margin_ok(body, D, need):

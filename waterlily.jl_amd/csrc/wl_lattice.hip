@@ -8,6 +8,7 @@
 
 #include "wl_common.hpp"
 #include "wl_lattice.hpp"
+#include "wl_meshsdf.hpp"
 
 struct wl_sdf_lattice { int32_t id; int32_t D; int32_t n[3]; float* a; float edge_min; };
 
@@ -85,6 +86,64 @@ int wl_sdf_lattice_create(wl_sdf_lattice** out, int D, const int32_t* dims, cons
   g_lat[slot] = L;
   *out = L;
   return 0;
+}
+int wl_sdf_lattice_from_mesh(wl_sdf_lattice** out, int D, const int32_t* dims, const float* host_origin, float spacing, const float* host_vertices, int32_t nv,
+                             const int32_t* host_elems, int32_t ne, unsigned flags, void* st) {
+  WL_CHECK(out, "wl_sdf_lattice_from_mesh: null result"); *out = nullptr;
+  WL_CHECK(D == 2 || D == 3, "wl_sdf_lattice_from_mesh: D must be 2 or 3");
+  WL_CHECK(dims && host_origin && host_vertices && host_elems, "wl_sdf_lattice_from_mesh: null dims, origin, vertices or elements");
+  WL_CHECK((flags & ~(unsigned)WL_MESH_BRUTE) == 0, "wl_sdf_lattice_from_mesh: unknown flag");
+  size_t count = 1;
+  for (int q = 0; q < D; q++) {
+    WL_CHECK(dims[q] >= 3, "wl_sdf_lattice_from_mesh: every extent must be at least 3 (one cell and its ghost layer)");
+    WL_CHECK(dims[q] <= (1 << 20), "wl_sdf_lattice_from_mesh: extent out of range");
+    count *= (size_t)dims[q];
+  }
+  WL_CHECK(std::isfinite(spacing) && spacing > 0.f, "wl_sdf_lattice_from_mesh: the spacing must be finite and positive");
+  for (int q = 0; q < D; q++) WL_CHECK(std::isfinite(host_origin[q]), "wl_sdf_lattice_from_mesh: the origin is not finite");
+  wl::MeshTables tab;
+  WL_TRY(wl::meshsdf_prepare(D, host_vertices, nv, host_elems, ne, &tab));      // the refusals that concern the mesh; host only
+  std::lock_guard<std::mutex> lock(g_lat_mutex);
+  int slot = 0;
+  while (slot < WL_LATTICE_MAX && g_lat[slot]) slot++;
+  if (slot == WL_LATTICE_MAX) { wl_set_error("wl_sdf_lattice_from_mesh: WL_LATTICE_MAX (8) lattices are alive — destroy one first"); return WL_EINVAL; }
+  WL_TRY(wl_ctx_ensure());
+  wl_sdf_lattice* L = new wl_sdf_lattice{};
+  L->D = D;
+  for (int q = 0; q < 3; q++) L->n[q] = q < D ? dims[q] : 1;
+  std::vector<float> host(count);
+  hipError_t e = hipMalloc((void**)&L->a, count * sizeof(float));
+  int rc = (int)e;
+  if (e != hipSuccess) wl_set_error(std::string("wl_sdf_lattice_from_mesh: ") + hipGetErrorString(e));
+  else rc = wl::meshsdf_run(tab, L->n, host_origin, spacing, flags, L->a, host.data(), wl_stream(st));      // synchronises the stream, like create
+  if (rc != 0) {
+    if (L->a) (void)hipFree(L->a);
+    delete L;
+    return rc;
+  }
+  L->edge_min = edge_min_of(D, L->n, host.data());
+  L->id = g_lat_next_id++;
+  g_lat[slot] = L;
+  *out = L;
+  return 0;
+}
+int wl_sdf_lattice_read(const wl_sdf_lattice* L, float* host_values, void* st) {
+  WL_CHECK(L && host_values, "wl_sdf_lattice_read: null lattice or values");
+  std::lock_guard<std::mutex> lock(g_lat_mutex);
+  int slot = 0;
+  while (slot < WL_LATTICE_MAX && g_lat[slot] != L) slot++;
+  WL_CHECK(slot < WL_LATTICE_MAX, "wl_sdf_lattice_read: not a live lattice");
+  const size_t count = (size_t)L->n[0] * (size_t)L->n[1] * (size_t)L->n[2];
+  hipStream_t s = wl_stream(st);
+  WL_HIP(hipMemcpyAsync(host_values, L->a, count * sizeof(float), hipMemcpyDeviceToHost, s));
+  WL_HIP(hipStreamSynchronize(s));
+  return 0;
+}
+float wl_sdf_lattice_edge_min(const wl_sdf_lattice* L) {
+  if (!L) return 0.f;
+  std::lock_guard<std::mutex> lock(g_lat_mutex);
+  for (const wl_sdf_lattice* q : g_lat) if (q == L) return L->edge_min;
+  return 0.f;
 }
 int wl_sdf_lattice_destroy(wl_sdf_lattice* L) {
   if (!L) return 0;
