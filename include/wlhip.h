@@ -480,6 +480,43 @@ int   wl_sdf_lattice_from_mesh(wl_sdf_lattice** out, int D, const int32_t* dims,
 int   wl_sdf_lattice_read(const wl_sdf_lattice* lattice, float* host_values, void* hip_stream);  /* the samples, first index fastest; synchronises */
 float wl_sdf_lattice_edge_min(const wl_sdf_lattice* lattice);                                    /* what create recorded; 0 for NULL / not alive */
 
+/* ---- deforming meshes: vertex velocities sampled into the lattice, and re-baking a lattice in place ----
+ * A lattice may carry velocity samples W next to its distances A: D component planes of dims[0]·…·dims[D−1] floats each, component-major, first index
+ * fastest inside a plane, like every vector array of the library.  They hold the velocity ξ̇ of the surface in the BODY frame, in flow-grid cells per unit
+ * time, extended off the surface.  The leaf WL_BODY_LATTICE of such a lattice, past the d² > fastd² exit and the NaN exit (where n = V = 0 stays), samples
+ *     ωξ_c = interp(q, W_c),  c < D          the cell, the weights and the clamp of the distance; the 2^D corners in the same order, Float32, uncontracted
+ * and returns   unmapped: V = ωξ      mapped: V_a = (V + ω×(x−x₀−xₚ))_a + Σ_q R̂[q][a]·ωξ_q   (the sum left to right from 0; ẋ = R̂ᵀξ̇ + the rigid part —
+ * the same R̂ᵀ that carries the gradient to n).  A lattice without velocity samples, and every other leaf, returns the bits it returned before.  The velocity
+ * belongs to the lattice: wl_body_node, wl_rigid_map and wl_bodyset are unchanged.
+ *
+ * wl_sdf_lattice_from_moving_mesh is wl_sdf_lattice_from_mesh — the same refusals, the same search, the same distance bits on every sample — plus velocity
+ * samples: host_vertex_velocity holds nv rows of D floats, and each sample stores the velocity of its closest surface point, the winner's vertex velocities
+ * wa, wb, wc combined with the barycentric pair (v, w) of the region the walk decided (vertex A (0,0), B (1,0), C (0,1); edge AB (v,0), CA (0,w), BC (1−w,w);
+ * face (v,w); 2-D: v ∈ {0, 1, t/den}):   W = wa + v·(wb − wa) + w·(wc − wa)   per component, Float32, in this order, uncontracted — a uniform vertex
+ * velocity U gives W = U exactly.  Culled and WL_MESH_BRUTE runs store the same W bits.  On the medial axis of the surface, where the closest point jumps,
+ * W is discontinuous; a body's band |d| ≤ 2 + ϵ stays clear of it wherever the surface's radius of curvature does.  Also refused: a NULL or non-finite velocity.
+ *
+ * wl_sdf_lattice_update_mesh re-bakes a lattice that one of the two mesh calls made, in place, from moved vertices (nv rows, the connectivity of its
+ * creation) and, for a lattice with velocity samples, new vertex velocities (NULL = zeros).  Id, dims, origin, spacing and the device pointers stay: every
+ * program that names the lattice — a handle's body, a force recorder, the last wl_sim_forces_bodyset — picks the new shape up at its next launch (the force
+ * band's tile list is rebuilt by the next measure! of the handle, as after any change of the body).  edge_min is recorded again; a surface that has moved
+ * too close to the lattice's edge is refused by the next measure!/force call through the out-of-range rule, not here.  The launch is queued on hip_stream, so
+ * earlier work on that stream that reads the lattice is ordered before it (work on OTHER streams that still reads it is the caller's to order); the call
+ * synchronises hip_stream.  WL_EINVAL on the host, with nothing launched and samples, velocity samples, edge_min and the kept vertices exactly as they were,
+ * for: every mesh refusal of wl_sdf_lattice_from_mesh on the moved vertices (non-finite, zero area, signed volume not positive); a lattice not made from a
+ * mesh; a lattice that is not alive; a non-NULL velocity on a lattice made without velocity samples; a non-finite velocity; an unknown flag.
+ *
+ * wl_sdf_lattice_set_velocity attaches or replaces the velocity samples of ANY live lattice from host_w[D·count] (all finite) — for a caller whose own tool
+ * made them; wl_sdf_lattice_read_velocity copies them to the host (WL_EINVAL if there are none); both work on hip_stream and synchronise it.
+ * wl_sdf_lattice_has_velocity: 1 / 0 (0 for NULL or a handle that is not alive).  The stream scenario of all of these is tests/test_gpu_streams_meshvel.py. */
+int wl_sdf_lattice_from_moving_mesh(wl_sdf_lattice** out, int D, const int32_t* dims, const float* host_origin, float spacing,
+                                    const float* host_vertices, int32_t nv, const int32_t* host_elems, int32_t ne,
+                                    const float* host_vertex_velocity, unsigned flags, void* hip_stream);
+int wl_sdf_lattice_update_mesh(wl_sdf_lattice* lattice, const float* host_vertices, const float* host_vertex_velocity, unsigned flags, void* hip_stream);
+int wl_sdf_lattice_set_velocity(wl_sdf_lattice* lattice, const float* host_w, void* hip_stream);
+int wl_sdf_lattice_read_velocity(const wl_sdf_lattice* lattice, float* host_w, void* hip_stream);
+int wl_sdf_lattice_has_velocity(const wl_sdf_lattice* lattice);
+
 /* ---- force history: pressure/viscous force and moment of a body after every step, from the body's band only (src/Metrics.jl:116-195) --------
  * nds(body,x) is zero outside |d| ≤ 1, so the sums run over a list of ACTIVE TILES — boxes of 64×4×4 array cells (2-D: 64×4) with an interior cell at
  * d² ≤ 1, found by evaluating the body program on every interior cell, in ascending order, rebuilt only when the body changes.  One launch with one

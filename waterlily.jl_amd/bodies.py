@@ -162,6 +162,7 @@ class SdfLattice:
             raise ValueError("SdfLattice: values must be a 2-D or 3-D array")
         self.D, self.dims = a.ndim, tuple(int(n) for n in a.shape)
         self.edge_min = edge_min(a) if min(self.dims) >= 3 else 0.0
+        self.vertices = None                                         # not from a mesh
         flat = np.ascontiguousarray(a.reshape(-1, order="F"))        # first index fastest, as every array of the library
         h = C.c_void_p()
         self._h = None
@@ -170,11 +171,13 @@ class SdfLattice:
         self.id = int(lib().wl_sdf_lattice_id(h))
 
     @classmethod
-    def from_mesh(cls, vertices, elems, dims, origin=0, spacing=1, brute=False):
+    def from_mesh(cls, vertices, elems, dims, origin=0, spacing=1, brute=False, vertex_velocity=None):
         """the exact signed distance to a closed surface, sampled on the device (wl_sdf_lattice_from_mesh): `vertices` (nv × D) in the body frame, in flow-grid
         cells; `elems` (ne × 3) triangles in 3-D, (ne × 2) segments of closed polygons in 2-D, oriented outward (counter-clockwise seen from the fluid);
         sample i sits at origin + spacing·(i − ½), as for centres().  Negative inside.  brute=True tests every (sample, element) pair instead of culling: the
-        same bits, for tests and timings.  A mesh that is open, non-manifold, unwelded (see weld) or oriented inward raises WlError with the reason."""
+        same bits, for tests and timings.  A mesh that is open, non-manifold, unwelded (see weld) or oriented inward raises WlError with the reason.
+        `vertex_velocity` (nv × D, body frame, cells per unit time) makes a DEFORMING body of it (wl_sdf_lattice_from_moving_mesh): the lattice also samples
+        the velocity of the closest surface point, the leaf adds it to V, and update_mesh / advance re-bake it in place as the vertices move."""
         v = np.ascontiguousarray(vertices, dtype=f32)
         e = np.ascontiguousarray(elems, dtype=np.int32)
         if v.ndim != 2 or v.shape[1] not in (2, 3) or e.ndim != 2 or e.shape[1] != v.shape[1]:
@@ -187,13 +190,79 @@ class SdfLattice:
         self = cls.__new__(cls)
         self.D, self.dims, self._h = D, dims, None
         h = C.c_void_p()
-        check(lib().wl_sdf_lattice_from_mesh(C.byref(h), D, (C.c_int32 * D)(*dims), o.ctypes.data_as(C.POINTER(C.c_float)), float(spacing),
-                                             v.ctypes.data_as(C.POINTER(C.c_float)), len(v), e.ctypes.data_as(C.POINTER(C.c_int32)), len(e),
-                                             1 if brute else 0, None))
+        fp = C.POINTER(C.c_float)
+        if vertex_velocity is None:
+            check(lib().wl_sdf_lattice_from_mesh(C.byref(h), D, (C.c_int32 * D)(*dims), o.ctypes.data_as(fp), float(spacing),
+                                                 v.ctypes.data_as(fp), len(v), e.ctypes.data_as(C.POINTER(C.c_int32)), len(e), 1 if brute else 0, None))
+        else:
+            wv = self._velocity_rows(vertex_velocity, v)
+            check(lib().wl_sdf_lattice_from_moving_mesh(C.byref(h), D, (C.c_int32 * D)(*dims), o.ctypes.data_as(fp), float(spacing), v.ctypes.data_as(fp), len(v),
+                                                        e.ctypes.data_as(C.POINTER(C.c_int32)), len(e), wv.ctypes.data_as(fp), 1 if brute else 0, None))
         self._h = h
         self.id = int(lib().wl_sdf_lattice_id(h))
         self.edge_min = float(lib().wl_sdf_lattice_edge_min(h))      # recorded by the library from the samples it made
+        self.vertices = v.copy()                                     # of the last bake: what advance differences against
         return self
+
+    @staticmethod
+    def _velocity_rows(vertex_velocity, v):
+        wv = np.ascontiguousarray(vertex_velocity, dtype=f32)
+        if wv.shape != v.shape:
+            raise ValueError(f"vertex_velocity must have the shape of the vertices {v.shape}, not {wv.shape}")
+        return wv
+
+    def _live(self, who):
+        if self._h is None:
+            raise ValueError(f"SdfLattice.{who}: the lattice has been closed")
+        return self._h
+
+    @property
+    def has_velocity(self):
+        """whether the lattice carries velocity samples (wl_sdf_lattice_has_velocity)"""
+        return self._h is not None and bool(lib().wl_sdf_lattice_has_velocity(self._h))
+
+    def update_mesh(self, vertices, vertex_velocity=None, brute=False):
+        """re-bake this lattice IN PLACE from moved vertices (wl_sdf_lattice_update_mesh): the connectivity of its creation, the same id, dims, origin and
+        spacing — every body, recorder and handle that names it picks the new shape up at its next launch (sim_step_(remeasure=True)).  vertex_velocity=None
+        stores zero velocities (on a lattice made with velocity samples).  A refused update (WlError: an inverted or degenerate mesh, a non-finite value,
+        a lattice not from a mesh) changes nothing."""
+        h = self._live("update_mesh")
+        if self.vertices is None:
+            raise ValueError("SdfLattice.update_mesh: the lattice was not made from a mesh")
+        v = np.ascontiguousarray(vertices, dtype=f32)
+        if v.shape != self.vertices.shape:
+            raise ValueError(f"update_mesh: vertices must keep the shape {self.vertices.shape} of the lattice's mesh, not {v.shape}")
+        fp = C.POINTER(C.c_float)
+        wv = None if vertex_velocity is None else self._velocity_rows(vertex_velocity, v)
+        check(lib().wl_sdf_lattice_update_mesh(h, v.ctypes.data_as(fp), None if wv is None else wv.ctypes.data_as(fp), 1 if brute else 0, None))
+        self.edge_min = float(lib().wl_sdf_lattice_edge_min(h))
+        self.vertices = v.copy()
+
+    def advance(self, new_vertices, dt):
+        """move the surface to `new_vertices` over the time dt: vertex velocities (new − vertices)/dt in Float32, then update_mesh — one call per time step
+        of a deforming body"""
+        if self.vertices is None:
+            raise ValueError("SdfLattice.advance: the lattice was not made from a mesh")
+        new = np.ascontiguousarray(new_vertices, dtype=f32)
+        if new.shape != self.vertices.shape:
+            raise ValueError(f"advance: vertices must keep the shape {self.vertices.shape} of the lattice's mesh, not {new.shape}")
+        self.update_mesh(new, ((new - self.vertices) / f32(dt)).astype(f32))
+
+    def set_velocity(self, W):
+        """attach or replace the velocity samples from W of shape dims + (D,) (wl_sdf_lattice_set_velocity) — on any lattice, from any tool"""
+        h = self._live("set_velocity")
+        W = np.asarray(W, dtype=f32)
+        if W.shape != self.dims + (self.D,):
+            raise ValueError(f"set_velocity: W must have the shape {self.dims + (self.D,)}, not {W.shape}")
+        flat = np.ascontiguousarray(W.reshape(-1, order="F"))          # component-major, first index fastest inside a plane
+        check(lib().wl_sdf_lattice_set_velocity(h, flat.ctypes.data_as(C.POINTER(C.c_float)), None))
+
+    def velocity(self):
+        """the velocity samples as an ndarray of shape dims + (D,), read back from the device (wl_sdf_lattice_read_velocity)"""
+        h = self._live("velocity")
+        flat = np.empty(int(np.prod(self.dims)) * self.D, dtype=f32)
+        check(lib().wl_sdf_lattice_read_velocity(h, flat.ctypes.data_as(C.POINTER(C.c_float)), None))
+        return flat.reshape(self.dims + (self.D,), order="F")
 
     def values(self):
         """the samples as an ndarray of shape `dims`, read back from the device (wl_sdf_lattice_read)"""
@@ -260,15 +329,16 @@ def mesh_placement(vertices, spacing=1.0, margin=5.0):
     return dims, tuple(float(lo[d] - margin - spacing / 2.0) for d in range(v.shape[1]))
 
 
-def mesh_body(vertices, elems, spacing=1.0, margin=None, offset=0.0, map=None):
+def mesh_body(vertices, elems, spacing=1.0, margin=None, offset=0.0, map=None, vertex_velocity=None):
     """A closed triangle mesh (2-D: closed polygons of segments) as a body: its exact signed distance sampled at `spacing` into a lattice around its
     bounding box (SdfLattice.from_mesh, mesh_placement) and the lattice leaf over it — Body(("lattice", lat, origin, spacing, offset), map).  Vertices are
     in the body frame, in flow-grid cells; `map` places and moves the body.  The lattice every sample of which lies `margin` or more outside the box has
     edge_min ≥ margin; margin=None takes 5 + |offset|, which satisfies measure!'s rule edge_min − |offset| > 2 + ϵ + 1 at ϵ = 1 — a larger ϵ needs a
-    larger margin (ϵ + 4 + |offset|).  The lattice is the body's: body.shape[1].close() frees it (at most LATTICE_MAX are alive)."""
+    larger margin (ϵ + 4 + |offset|).  The lattice is the body's: body.shape[1].close() frees it (at most LATTICE_MAX are alive).  With `vertex_velocity`
+    (nv × D) the body deforms: body.shape[1].advance(new_vertices, dt) re-bakes it in place each step — lay the lattice (margin) around every shape it takes."""
     margin = 5.0 + abs(float(offset)) if margin is None else float(margin)
     dims, origin = mesh_placement(vertices, float(spacing), margin)
-    lat = SdfLattice.from_mesh(vertices, elems, dims, origin, spacing)
+    lat = SdfLattice.from_mesh(vertices, elems, dims, origin, spacing, vertex_velocity=vertex_velocity)
     return Body(("lattice", lat, origin, float(spacing), float(offset)), map)
 
 

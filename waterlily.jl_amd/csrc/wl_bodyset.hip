@@ -33,14 +33,14 @@ __global__ void __launch_bounds__(WL_BLOCK) k_measure_set(GridX g, float* __rest
     const float d2 = (2 + e) * (2 + e);
     float dc;
     if (P.leaf_root) dc = leaf_sdf<D>(P.node[0], P.lat, x);
-    else { float nq[3], vq[3]; set_measure<D, S>(P, x, d2, dc, nq, vq); }
+    else { float nq[3], vq[3]; set_measure<D, S>(P, x, d2, dc, nq, vq); }      // (d alone: no velocity samples read)
     sig[o] = dc;
     if (dc * dc < d2) {
 #pragma unroll
       for (int a = 0; a < D; a++) {
         float xf[3]; for (int q = 0; q < 3; q++) xf[q] = x[q] - ((q == a) ? 0.5f : 0.f);
         float di, ni[3], vi[3];
-        set_measure<D, S>(P, xf, d2, di, ni, vi);
+        set_measure<D, S, DS_V>(P, xf, d2, di, ni, vi);
         di = fabsf(di) <= 0.5f ? di : copysignf(di, dc);
         vv[a] = vi[a];
         m0[a] = mu0_(di, e);
@@ -133,7 +133,7 @@ __global__ void __launch_bounds__(WL_BLOCK) k_points_set(SetArg P, const float* 
   const int p = blockIdx.x * WL_BLOCK + threadIdx.x;
   if (p >= npts) return;
   float xp[3] = {0.f, 0.f, 0.f}; for (int q = 0; q < D; q++) xp[q] = x[(long)p * D + q];
-  float dd, nn[3], vv[3]; set_measure<D, S>(P, xp, fastd2, dd, nn, vv);
+  float dd, nn[3], vv[3]; set_measure<D, S, DS_V>(P, xp, fastd2, dd, nn, vv);
   d[p] = dd;
   for (int q = 0; q < D; q++) { n[(long)p * D + q] = nn[q]; v[(long)p * D + q] = vv[q]; }
 }
@@ -161,7 +161,9 @@ static int prepare_lattice_leaf(int D, const wl_body_node& a, wl_body_node& b, S
   return 0;
 }
 int bodyset_resolve(int D, SetArg* P) {
-  for (int q = 0; q < P->nlat; q++) { float edge; WL_TRY(wl::lattice_resolve(P->lat[q].id, D, &P->lat[q], &edge)); }
+  // gen stays what it was when the program was stored: a tile list built from it belongs to that filling of the lattice, and the next build against a freshly
+  // prepared program (ForceBand::build compares the bytes) then sees that the lattice has been re-filled in place since
+  for (int q = 0; q < P->nlat; q++) { float edge; const int32_t gen = P->lat[q].gen; WL_TRY(wl::lattice_resolve(P->lat[q].id, D, &P->lat[q], &edge)); P->lat[q].gen = gen; }
   return 0;
 }
 int bodyset_lattice_margin(const SetArg& P, float need, const char* who) {
@@ -236,7 +238,7 @@ int bodyset_from_body(int D, const wl_body* b, SetArg* out) {
 }
 int bodyset_measure_fields(float* sigma, float* mu0, float* mu1, float* V, const GridX& G, const SetArg& P, float eps, int exitBC, unsigned perdir, hipStream_t q) {
   WL_TRY(bodyset_lattice_margin(P, 2.f + eps + 1.f, "measure!"));      // every interior cell and face outside a lattice's box takes the early exit at fastd² = (2+ϵ)²
-  BSEL(G.D, P.depth, k_measure_set, wl_plane_grid(G, G.nz), dim3(WL_BLOCK), 0, q, G, sigma, mu0, mu1, V, P, eps);
+  BSELV(G.D, P.depth, setarg_has_velocity(P), k_measure_set, wl_plane_grid(G, G.nz), dim3(WL_BLOCK), 0, q, G, sigma, mu0, mu1, V, P, eps);
   WL_LAUNCH_CHECK();
   const float zero[3] = {0, 0, 0};
   WL_TRY(wl::bc_vec(mu0, G, zero, 0, perdir, q));                                                                                   // Body.jl:49
@@ -292,7 +294,7 @@ int wl_bodyset_measure_points(const wl_bodyset* set, int D, const float* hx, int
   int rc = 0;
   auto run = [&]() -> int {
     WL_HIP(hipMemcpyAsync(dx, hx, sizeof(float) * nx, hipMemcpyHostToDevice, q));
-    BSEL(D, P.depth, k_points_set, dim3((unsigned)((npts + WL_BLOCK - 1) / WL_BLOCK)), dim3(WL_BLOCK), 0, q, P, dx, npts, fastd2, dd, dn, dv);
+    BSELV(D, P.depth, setarg_has_velocity(P), k_points_set, dim3((unsigned)((npts + WL_BLOCK - 1) / WL_BLOCK)), dim3(WL_BLOCK), 0, q, P, dx, npts, fastd2, dd, dn, dv);
     WL_LAUNCH_CHECK();
     WL_HIP(hipMemcpyAsync(hd, dd, sizeof(float) * npts, hipMemcpyDeviceToHost, q));
     WL_HIP(hipMemcpyAsync(hn, dn, sizeof(float) * nx, hipMemcpyDeviceToHost, q));

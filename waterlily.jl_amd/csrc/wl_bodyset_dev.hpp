@@ -43,8 +43,10 @@ __device__ __forceinline__ float leaf_sdf(const wl_body_node& b, const LatRef* l
   to_body_frame<D>(b, x, xi, bq);
   return leaf_sdf_at<D>(b, lat, xi);
 }
-// measure(leaf,x;fastd²) -> d, n, V (n = V = 0 on the early exits)   src/AutoBody.jl:29-37
-template <int D>
+// measure(leaf,x;fastd²) -> d, n, V (n = V = 0 on the early exits)   src/AutoBody.jl:29-37.  VEL: the instantiation that adds a lattice's velocity samples to V —
+// launched only for a program that names a lattice which has some (setarg_has_velocity), and never by the force kernels, which do not read V: every other
+// launch runs the statements it ran before the samples existed
+template <int D, bool VEL>
 __device__ __forceinline__ void leaf_measure(const wl_body_node& b, const LatRef* lat, const float* x, float fastd2, float& d, float* n, float* v) {
   for (int q = 0; q < 3; q++) { n[q] = 0.f; v[q] = 0.f; }
   if (!b.mapped && (b.kind == WL_BODY_SPHERE || b.kind == WL_BODY_PLANE)) {          // the closed-form wl_body: V = its translation velocity (wl::bodyset_from_body; 0 in every public program)
@@ -56,13 +58,15 @@ __device__ __forceinline__ void leaf_measure(const wl_body_node& b, const LatRef
   d = leaf_sdf_at<D>(b, lat, xi);
   if (d * d > fastd2) return;
   float g[3] = {0.f, 0.f, 0.f}; bool nan = false;
+  float wx[3] = {0.f, 0.f, 0.f}; bool hasw = false;        // a lattice leaf with velocity samples: ωξ, sampled with the gradient (one cell, one set of weights)
   if (b.kind == WL_BODY_PLANE) { for (int q = 0; q < D; q++) g[q] = b.m[q]; }
   else if (b.kind == WL_BODY_SPHERE) {
     float s = 0.f; for (int q = 0; q < D; q++) { const float dx = b.m[q] * (xi[q] - b.c[q]); s += dx * dx; }
     const float rr = sqrtf(s);
     for (int q = 0; q < D; q++) g[q] = (b.m[q] * (xi[q] - b.c[q])) / rr;
   } else if (b.kind == WL_BODY_LATTICE) {                  // the one leaf whose |∇sdf| is whatever the samples say: d /= m below does real work
-    lattice_grad<D>(lat[__float_as_int(b.h)], b.c, b.m[0], xi, g);
+    if constexpr (VEL) hasw = lattice_grad_vel<D>(lat[__float_as_int(b.h)], b.c, b.m[0], xi, g, wx);
+    else lattice_grad<D>(lat[__float_as_int(b.h)], b.c, b.m[0], xi, g);
   } else {
     float t = 0.f; for (int q = 0; q < D; q++) t += b.m[q] * (xi[q] - b.c[q]);
     t = fminf(fmaxf(t, -b.h), b.h);
@@ -86,11 +90,15 @@ __device__ __forceinline__ void leaf_measure(const wl_body_node& b, const LatRef
       v[2] = b.map.V[2] + (b.map.w[0] * bq[1] - b.map.w[1] * bq[0]);
     }
   }
+  if (VEL && hasw) {                                      // a deforming surface: ẋ = R̂ᵀξ̇ + the rigid part (wave-uniform: the lattices are kernel arguments)
+    if (b.mapped) { for (int a = 0; a < D; a++) { float s = 0.f; for (int q = 0; q < D; q++) s += b.map.R[q * 3 + a] * wx[q]; v[a] = v[a] + s; } }
+    else { for (int a = 0; a < D; a++) v[a] = wx[a]; }
+  }
 }
 
 // measure(body::SetBody,x;fastd²): the postfix program on a per-lane stack of S tuples (d,n,V).  The stack pointer is wave-uniform
 // (it follows the program), so every access is an unrolled compare against a scalar: the stack lives in registers, never in scratch.
-template <int D, int S>
+template <int D, int S, bool VEL = false>
 __device__ __forceinline__ void set_measure(const SetArg& P, const float* x, float fastd2, float& d, float* n, float* v) {
   constexpr int W = 2 * D + 1;                            // tuple width
   float st[S][W];
@@ -99,7 +107,7 @@ __device__ __forceinline__ void set_measure(const SetArg& P, const float* x, flo
     const wl_body_node& nd = P.node[i];
     if (nd.op == WL_OP_LEAF) {
       float dd, nq[3], vq[3];
-      leaf_measure<D>(nd, P.lat, x, fastd2, dd, nq, vq);
+      leaf_measure<D, VEL>(nd, P.lat, x, fastd2, dd, nq, vq);
 #pragma unroll
       for (int s = 0; s < S; s++)
         if (s == sp) { st[s][0] = dd; for (int q = 0; q < D; q++) { st[s][1 + q] = nq[q]; st[s][1 + D + q] = vq[q]; } }
@@ -172,13 +180,24 @@ __device__ __forceinline__ void cell_centre(const GridX& g, int i, int j, int k,
   for (int q = 0; q < 3; q++) x[q] = (float)I[q] - 1.5f;
 }
 }  // namespace
-// kernels are templated on DS = 16·D + S (dimension, stack slots) so that one DSEL-style macro picks the instantiation
-#define DS_D (DS / 16)
+// kernels are templated on DS = 16·D + S (dimension, stack slots; + 64: the instantiation that reads a lattice's velocity samples) so that one DSEL-style
+// macro picks the instantiation
+#define DS_D ((DS / 16) % 4)
 #define DS_S (DS % 16)
+#define DS_V (DS / 64 != 0)
+// whether a program names a lattice that carries velocity samples (host; the lattices as last resolved)
+static inline bool setarg_has_velocity(const SetArg& P) { for (int q = 0; q < P.nlat; q++) if (P.lat[q].w) return true; return false; }
 
 // instantiations: stack of 2 (every left-deep chain a∘b∘c∘…, a single leaf) or WL_BODYSET_STACK slots
 #define BSEL(D, S, KERN, ...)                                                                                                        \
   do {                                                                                                                                \
     if ((D) == 3) { if ((S) <= 2) hipLaunchKernelGGL(KERN<50>, __VA_ARGS__); else hipLaunchKernelGGL(KERN<48 + WL_BODYSET_STACK>, __VA_ARGS__); } \
     else { if ((S) <= 2) hipLaunchKernelGGL(KERN<34>, __VA_ARGS__); else hipLaunchKernelGGL(KERN<32 + WL_BODYSET_STACK>, __VA_ARGS__); }           \
+  } while (0)
+// … for the kernels that hand V on (measure!, the point probe): V != 0 picks the instantiations with the velocity samples
+#define BSELV(D, S, V, KERN, ...)                                                                                                     \
+  do {                                                                                                                                \
+    if (!(V)) { BSEL(D, S, KERN, __VA_ARGS__); }                                                                                      \
+    else if ((D) == 3) { if ((S) <= 2) hipLaunchKernelGGL(KERN<64 + 50>, __VA_ARGS__); else hipLaunchKernelGGL(KERN<64 + 48 + WL_BODYSET_STACK>, __VA_ARGS__); } \
+    else { if ((S) <= 2) hipLaunchKernelGGL(KERN<64 + 34>, __VA_ARGS__); else hipLaunchKernelGGL(KERN<64 + 32 + WL_BODYSET_STACK>, __VA_ARGS__); }               \
   } while (0)

@@ -159,7 +159,7 @@ int ForceBand::run(const GridX& G, const float* p, const float* u, float nu, con
   WL_LAUNCH_CHECK();
   return 0;
 }
-int ForceBand::recheck(int D) { return valid ? bodyset_resolve(D, &P) : 0; }
+int ForceBand::recheck(int D) { return valid ? bodyset_resolve(D, &P) : 0; }      // (resolving keeps LatRef::gen as stored: see wl::bodyset_resolve)
 void ForceBand::release() {
   if (flag) (void)hipFree(flag);
   if (out) (void)hipFree(out);

@@ -10,7 +10,9 @@
 // under brute force is the first that attains the computed minimum, it is a candidate (its true distance is at most Ub), so both forms store the same bits.
 // No list is kept (the ballot is the list, 64 entries at a time, consumed at once: any candidate count works), no atomics, nothing between workgroups.
 // The sign: (p − q)·n with the angle-weighted pseudonormal of the winning feature (Bærentzen & Aanæs 2005), gathered once per sample after the search.
+#include <chrono>
 #include <cmath>
+#include <string>
 #include <unordered_map>
 
 #include "wl_meshsdf.hpp"
@@ -21,14 +23,19 @@ struct MsArgs {
   const float* elem; const float4* sph; const float* nrm; float* a; unsigned long long* pairs;
   int32_t ne; int32_t n[3]; int32_t nb[3]; long nbricks;
   float c[3]; float s; float rb; float slack; int brute;
+  const float* wtab; float* w;      // VEL: the vertex velocities per element (ne×D×D, vertex-major like elem) and the D component planes they are extended into
 };
 unsigned long long g_ms_tested = 0, g_ms_total = 0;      // wl_meshsdf_last_pairs
+double g_ms_ms[4] = {0, 0, 0, 0};                        // wl_meshsdf_last_times
+int g_ms_timed = 0;
 }  // namespace
 
 #pragma clang fp contract(off)
 namespace {
-// the closest point q of element e (vertices in LDS) to p: r = p − q, d² = |r|², reg = the region of the walk (the row of the pseudonormal table)
-__device__ __forceinline__ void ms_pair(const float* e, const float (&p)[3], float& d2, int& reg, float (&r)[3]) {
+// the closest point q of element e (vertices in LDS) to p: r = p − q, d² = |r|², reg = the region of the walk (the row of the pseudonormal table).
+// VEL: also the barycentric pair (bv, bw) of q = A + bv·(B − A) + bw·(C − A), read off the region the walk decides — never solved for again
+template <bool VEL>
+__device__ __forceinline__ void ms_pair(const float* e, const float (&p)[3], float& d2, int& reg, float (&r)[3], float& bv, float& bw) {
   const float a[3] = {e[0], e[1], e[2]}, b[3] = {e[3], e[4], e[5]}, c[3] = {e[6], e[7], e[8]};
   float ab[3], ac[3], ap[3], q[3];
 #pragma unroll
@@ -44,35 +51,42 @@ __device__ __forceinline__ void ms_pair(const float* e, const float (&p)[3], flo
   const float vc = d1 * d4 - d3 * d2_, vb = d5 * d2_ - d1 * d6, va = d3 * d6 - d5 * d4;
   if (d1 <= 0.f && d2_ <= 0.f) {                                            // vertex A
     reg = 4;
+    if constexpr (VEL) { bv = 0.f; bw = 0.f; }
 #pragma unroll
     for (int k = 0; k < 3; k++) q[k] = a[k];
   } else if (d3 >= 0.f && d4 <= d3) {                                       // vertex B
     reg = 5;
+    if constexpr (VEL) { bv = 1.f; bw = 0.f; }
 #pragma unroll
     for (int k = 0; k < 3; k++) q[k] = b[k];
   } else if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {                         // edge AB
     reg = 1;
     const float v = d1 / (d1 - d3);
+    if constexpr (VEL) { bv = v; bw = 0.f; }
 #pragma unroll
     for (int k = 0; k < 3; k++) q[k] = a[k] + v * ab[k];
   } else if (d6 >= 0.f && d5 <= d6) {                                       // vertex C
     reg = 6;
+    if constexpr (VEL) { bv = 0.f; bw = 1.f; }
 #pragma unroll
     for (int k = 0; k < 3; k++) q[k] = c[k];
   } else if (vb <= 0.f && d2_ >= 0.f && d6 <= 0.f) {                        // edge CA
     reg = 3;
     const float w = d2_ / (d2_ - d6);
+    if constexpr (VEL) { bv = 0.f; bw = w; }
 #pragma unroll
     for (int k = 0; k < 3; k++) q[k] = a[k] + w * ac[k];
   } else if (va <= 0.f && (d4 - d3) >= 0.f && (d5 - d6) >= 0.f) {           // edge BC
     reg = 2;
     const float w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+    if constexpr (VEL) { bv = 1.f - w; bw = w; }
 #pragma unroll
     for (int k = 0; k < 3; k++) q[k] = b[k] + w * (c[k] - b[k]);
   } else {                                                                  // the face
     reg = 0;
     const float den = 1.f / ((va + vb) + vc);
     const float v = vb * den, w = vc * den;
+    if constexpr (VEL) { bv = v; bw = w; }
 #pragma unroll
     for (int k = 0; k < 3; k++) q[k] = (a[k] + ab[k] * v) + ac[k] * w;
   }
@@ -80,20 +94,22 @@ __device__ __forceinline__ void ms_pair(const float* e, const float (&p)[3], flo
   for (int k = 0; k < 3; k++) r[k] = p[k] - q[k];
   d2 = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
 }
-__device__ __forceinline__ void ms_pair(const float* e, const float (&p)[2], float& d2, int& reg, float (&r)[2]) {
+template <bool VEL>
+__device__ __forceinline__ void ms_pair(const float* e, const float (&p)[2], float& d2, int& reg, float (&r)[2], float& bv, float& bw) {
   const float a[2] = {e[0], e[1]}, b[2] = {e[2], e[3]};
   const float ab[2] = {b[0] - a[0], b[1] - a[1]}, ap[2] = {p[0] - a[0], p[1] - a[1]};
   const float t = ab[0] * ap[0] + ab[1] * ap[1];
   const float den = ab[0] * ab[0] + ab[1] * ab[1];
   float q[2];
-  if (t <= 0.f) { reg = 1; q[0] = a[0]; q[1] = a[1]; }                      // vertex A
-  else if (t >= den) { reg = 2; q[0] = b[0]; q[1] = b[1]; }                 // vertex B
-  else { reg = 0; const float v = t / den; q[0] = a[0] + v * ab[0]; q[1] = a[1] + v * ab[1]; }
+  if (t <= 0.f) { reg = 1; q[0] = a[0]; q[1] = a[1]; if constexpr (VEL) bv = 0.f; }                      // vertex A
+  else if (t >= den) { reg = 2; q[0] = b[0]; q[1] = b[1]; if constexpr (VEL) bv = 1.f; }                 // vertex B
+  else { reg = 0; const float v = t / den; q[0] = a[0] + v * ab[0]; q[1] = a[1] + v * ab[1]; if constexpr (VEL) bv = v; }
+  if constexpr (VEL) bw = 0.f;
   r[0] = p[0] - q[0]; r[1] = p[1] - q[1];
   d2 = r[0] * r[0] + r[1] * r[1];
 }
 
-template <int D>
+template <int D, bool VEL>
 __global__ __launch_bounds__(256) void k_meshsdf(const MsArgs A) {
   constexpr int NE = D * D, NR = D == 3 ? 7 : 3;
   constexpr int EXT[3] = {4, D == 3 ? 4 : 16, D == 3 ? 4 : 1};
@@ -138,6 +154,7 @@ __global__ __launch_bounds__(256) void k_meshsdf(const MsArgs A) {
   // sweep 2: the candidates of each staged chunk, exactly
   float best = INFINITY, br[D];
   int bt = 0, breg = 0;
+  float bbv = 0.f, bbw = 0.f;                              // VEL: the winner's barycentric pair
 #pragma unroll
   for (int d = 0; d < D; d++) br[d] = 0.f;
   unsigned long long ntest = 0;
@@ -166,10 +183,11 @@ __global__ __launch_bounds__(256) void k_meshsdf(const MsArgs A) {
       while (mask) {
         const int jj = k + __ffsll((long long)mask) - 1;
         mask &= mask - 1;
-        float d2, r[D]; int reg;
-        ms_pair(&s_e[jj * NE], p, d2, reg, r);
+        float d2, r[D], pv = 0.f, pw = 0.f; int reg;
+        ms_pair<VEL>(&s_e[jj * NE], p, d2, reg, r, pv, pw);
         if (d2 < best) {
           best = d2; bt = base + jj; breg = reg;
+          if constexpr (VEL) { bbv = pv; bbw = pw; }
 #pragma unroll
           for (int d = 0; d < D; d++) br[d] = r[d];
         }
@@ -185,6 +203,17 @@ __global__ __launch_bounds__(256) void k_meshsdf(const MsArgs A) {
     const float d = sqrtf(best);
     const size_t o = (size_t)i[0] + (size_t)A.n[0] * ((size_t)i[1] + (size_t)A.n[1] * (size_t)i[2]);
     A.a[o] = sg < 0.f ? -d : d;                            // d = 0 has p = q, sg = ±0: +0 is stored
+    if constexpr (VEL) {                                   // the closest-point extension of the vertex velocities: W = wa + v·(wb − wa) + w·(wc − wa), gathered once
+      const float* wt = A.wtab + (size_t)bt * NE;
+      const size_t plane = (size_t)A.n[0] * (size_t)A.n[1] * (size_t)A.n[2];
+#pragma unroll
+      for (int c = 0; c < D; c++) {
+        const float wa = wt[c], wb = wt[D + c];
+        float W = wa + bbv * (wb - wa);
+        if (D == 3) W = W + bbw * (wt[2 * D + c] - wa);
+        A.w[(size_t)c * plane + o] = W;
+      }
+    }
   }
 }
 }  // namespace
@@ -221,8 +250,8 @@ void bounding_sphere(const V3* p, int k, V3* c, double* r) {
 }  // namespace
 
 namespace wl {
-int meshsdf_prepare(int D, const float* v, int32_t nv, const int32_t* e, int32_t ne, MeshTables* out) {
-  const std::string F = "wl_sdf_lattice_from_mesh: ";
+int meshsdf_prepare(int D, const float* v, int32_t nv, const int32_t* e, int32_t ne, MeshTables* out, const char* who) {
+  const std::string F = std::string(who) + ": ";
   if (D == 3 ? (nv < 4 || ne < 4) : (nv < 3 || ne < 3)) {
     wl_set_error(F + (D == 3 ? "a closed surface has at least 4 vertices and 4 triangles" : "a closed polygon has at least 3 vertices and 3 segments"));
     return WL_EINVAL;
@@ -325,8 +354,30 @@ int meshsdf_prepare(int D, const float* v, int32_t nv, const int32_t* e, int32_t
   return 0;
 }
 
-int meshsdf_run(const MeshTables& m, const int32_t* n, const float* c, float s, unsigned flags, float* a_dev, float* a_host, hipStream_t st) {
+int meshsdf_velocities(int D, const float* w, int32_t nv, const int32_t* e, int32_t ne, MeshTables* out, const char* who) {
+  for (size_t q = 0; q < (size_t)nv * D; q++)
+    if (!std::isfinite(w[q])) { wl_set_error(std::string(who) + ": the velocity of vertex " + std::to_string(q / D) + " is not finite"); return WL_EINVAL; }
+  out->wtab.resize((size_t)ne * D * D);
+  for (int32_t t = 0; t < ne; t++)
+    for (int k = 0; k < D; k++)
+      for (int d = 0; d < D; d++) out->wtab[((size_t)t * D + k) * D + d] = w[(size_t)e[(size_t)D * t + k] * D + d];
+  return 0;
+}
+
+int meshsdf_run(const MeshTables& m, const int32_t* n, const float* c, float s, unsigned flags, float* a_dev, float* a_host, float* w_dev, hipStream_t st) {
   const int D = m.D;
+  const bool vel = w_dev != nullptr;
+  WL_CHECK(!vel || m.wtab.size() == m.elem.size(), "mesh search: velocity samples asked for without a velocity table");
+  using clk = std::chrono::steady_clock;
+  const bool timed = g_ms_timed != 0;                      // wl_meshsdf_time: the phases are fenced with stream synchronisations and timed on the host
+  auto t0 = clk::now();
+  auto lap = [&](int q) -> int {
+    if (!timed) return 0;
+    WL_HIP(hipStreamSynchronize(st));
+    const auto t1 = clk::now();
+    g_ms_ms[q] = std::chrono::duration<double, std::milli>(t1 - t0).count(); t0 = t1;
+    return 0;
+  };
   MsArgs A{};
   A.ne = m.ne; A.s = s; A.brute = (flags & WL_MESH_BRUTE) ? 1 : 0;
   const int ext[3] = {4, D == 3 ? 4 : 16, D == 3 ? 4 : 1};
@@ -348,21 +399,27 @@ int meshsdf_run(const MeshTables& m, const int32_t* n, const float* c, float s, 
   // one scratch block: pairs | spheres | vertices | normals, each 16-byte aligned
   auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
   const size_t b_pairs = up((size_t)A.nbricks * 8), b_sph = up(m.sph.size() * 4), b_elem = up(m.elem.size() * 4), b_nrm = up(m.nrm.size() * 4);
-  char* base = (char*)wl_scratch(b_pairs + b_sph + b_elem + b_nrm);
+  const size_t b_wtab = vel ? up(m.wtab.size() * 4) : 0;
+  char* base = (char*)wl_scratch(b_pairs + b_sph + b_elem + b_nrm + b_wtab);
   if (!base) return (int)hipErrorOutOfMemory;
   A.pairs = (unsigned long long*)base; A.sph = (const float4*)(base + b_pairs);
   A.elem = (const float*)(base + b_pairs + b_sph); A.nrm = (const float*)(base + b_pairs + b_sph + b_elem);
   A.a = a_dev;
+  A.wtab = vel ? (const float*)(base + b_pairs + b_sph + b_elem + b_nrm) : nullptr; A.w = w_dev;
   WL_HIP(hipMemcpyAsync((void*)A.sph, m.sph.data(), m.sph.size() * 4, hipMemcpyHostToDevice, st));
   WL_HIP(hipMemcpyAsync((void*)A.elem, m.elem.data(), m.elem.size() * 4, hipMemcpyHostToDevice, st));
   WL_HIP(hipMemcpyAsync((void*)A.nrm, m.nrm.data(), m.nrm.size() * 4, hipMemcpyHostToDevice, st));
-  if (D == 3) hipLaunchKernelGGL(k_meshsdf<3>, dim3((unsigned)nblocks), dim3(256), 0, st, A);
-  else hipLaunchKernelGGL(k_meshsdf<2>, dim3((unsigned)nblocks), dim3(256), 0, st, A);
+  if (vel) WL_HIP(hipMemcpyAsync((void*)A.wtab, m.wtab.data(), m.wtab.size() * 4, hipMemcpyHostToDevice, st));
+  WL_TRY(lap(1));
+  if (D == 3) { if (vel) hipLaunchKernelGGL((k_meshsdf<3, true>), dim3((unsigned)nblocks), dim3(256), 0, st, A); else hipLaunchKernelGGL((k_meshsdf<3, false>), dim3((unsigned)nblocks), dim3(256), 0, st, A); }
+  else { if (vel) hipLaunchKernelGGL((k_meshsdf<2, true>), dim3((unsigned)nblocks), dim3(256), 0, st, A); else hipLaunchKernelGGL((k_meshsdf<2, false>), dim3((unsigned)nblocks), dim3(256), 0, st, A); }
   WL_LAUNCH_CHECK();
+  WL_TRY(lap(2));
   std::vector<unsigned long long> pairs((size_t)A.nbricks);
   WL_HIP(hipMemcpyAsync(a_host, a_dev, count * sizeof(float), hipMemcpyDeviceToHost, st));
   WL_HIP(hipMemcpyAsync(pairs.data(), A.pairs, pairs.size() * 8, hipMemcpyDeviceToHost, st));
   WL_HIP(hipStreamSynchronize(st));
+  WL_TRY(lap(3));
   unsigned long long tested = 0;
   for (unsigned long long q : pairs) tested += q;
   g_ms_tested = tested; g_ms_total = (unsigned long long)count * (unsigned long long)m.ne;
@@ -370,6 +427,13 @@ int meshsdf_run(const MeshTables& m, const int32_t* n, const float* c, float s, 
 }
 }  // namespace wl
 
+extern "C" int wl_meshsdf_time(int on) { g_ms_timed = on ? 1 : 0; return 0; }
+void wl::meshsdf_note_tables_ms(double ms) { g_ms_ms[0] = ms; }
+extern "C" int wl_meshsdf_last_times(double* ms4) {
+  WL_CHECK(ms4, "wl_meshsdf_last_times: null result");
+  for (int q = 0; q < 4; q++) ms4[q] = g_ms_ms[q];
+  return 0;
+}
 extern "C" int wl_meshsdf_last_pairs(uint64_t* tested, uint64_t* total) {
   WL_CHECK(tested && total, "wl_meshsdf_last_pairs: null result");
   *tested = g_ms_tested; *total = g_ms_total;
