@@ -517,6 +517,41 @@ int wl_sdf_lattice_set_velocity(wl_sdf_lattice* lattice, const float* host_w, vo
 int wl_sdf_lattice_read_velocity(const wl_sdf_lattice* lattice, float* host_w, void* hip_stream);
 int wl_sdf_lattice_has_velocity(const wl_sdf_lattice* lattice);
 
+/* ---- band-limited baking: search only the bricks near the surface ----
+ * measure! reads a body only in the band |d| ≤ 2 + ϵ (the forces in |d| ≤ 1), yet the calls above search every sample of the lattice.  A lattice made by
+ * wl_sdf_lattice_from_mesh_band with a band b > 0 (distance units: flow-grid cells) is the full one, clipped: on EVERY sample it stores, as raw bits,
+ *     A_band = clip(A_full, −b, +b)          W_band = W_full where |A_full| ≤ b, else +0.0f in every component   (host_vertex_velocity non-NULL)
+ * with A_full, W_full what wl_sdf_lattice_from_mesh / _from_moving_mesh store for the same arguments; a clipped sample holds exactly +b or −b with the sign
+ * of A_full (a truncated signed distance field).  edge_min is recorded from the stored, clipped samples by the same function; wl_sdf_lattice_read returns
+ * them.  The search skips every brick of 4×4×4 (4×16) samples whose bounding spheres prove it wholly beyond the band — such a brick does not meet the
+ * surface, one sign search for its first sample serves all its samples — and clips at the store elsewhere (csrc/wl_meshsdf.hip, k_meshsdf<D, VEL, true>).
+ * With WL_MESH_BRUTE every (sample, element) pair is visited, no brick is skipped, and the same clip is applied: the same bits.
+ *
+ * The band is a property of the lattice, fixed at creation (wl_sdf_lattice_band; 0 for the three other creation calls, which work as ever):
+ * wl_sdf_lattice_update_mesh re-bakes with it, and a refused update leaves it, like everything else, as it was.  The call applies every refusal of
+ * wl_sdf_lattice_from_mesh (and, with velocities, of _from_moving_mesh), and one more: a band that is not finite and positive — WL_EINVAL with the reason,
+ * on the host, before any launch or device allocation.  The limit of 8 alive, ids, the stream behaviour (works on hip_stream and synchronises it; the
+ * scenario is tests/test_gpu_streams_meshband.py), wl_sdf_lattice_set_velocity, _read_velocity and _has_velocity are unchanged.
+ *
+ * The band rule.  For a lattice leaf over a banded lattice baked at spacing s, the calls that apply the out-of-range rule above (edge_min − |R| > need,
+ * need = 2 + ϵ + 1 for the calls that measure fields, 2 for the force calls) return WL_EINVAL before any launch unless also
+ *     band − |R| > need + s·√D
+ * and the message names the condition that failed with both numbers.  s is the spacing recorded at BAKING, not the m[0] of the leaf.
+ * wl_bodyset_measure_points applies neither rule.  Why this bound — the surface distance is 1-Lipschitz:
+ *   1. if one of the 2^D corners of a query's interpolation cell is clipped, |A_full| > b there, so no surface lies within s√D of that corner (b > s√D):
+ *      the whole cell lies on one side of the surface;
+ *   2. every corner of the cell then has |A_full| > b − s√D: the stored corners share one sign and each has magnitude ≥ b − s√D;
+ *   3. the interpolated value, a convex combination, has |v| ≥ b − s√D up to Float32 rounding, so |v − R| > need: the query takes the leaf's early exit
+ *      (d·d > fastd²), and the full lattice makes the same query take it for the same reason;
+ *   4. conversely a query that does not exit reads unclipped corners only: the value, gradient and velocity bits of the full lattice.
+ * So μ₀, μ₁, V, the force terms and every step are those of the full lattice bit for bit, under UNION / INTERSECT / NEGATE as well (a far leaf loses or
+ * wins a min / max identically; where it wins, both results are beyond the exit).  Only σ differs, and only where |σ_full| > 2 + ϵ: there it keeps its
+ * sign and stays above that magnitude. */
+int   wl_sdf_lattice_from_mesh_band(wl_sdf_lattice** out, int D, const int32_t* dims, const float* host_origin, float spacing,
+                                    const float* host_vertices, int32_t nv, const int32_t* host_elems, int32_t ne,
+                                    const float* host_vertex_velocity /* NULL: no velocity samples */, float band, unsigned flags, void* hip_stream);
+float wl_sdf_lattice_band(const wl_sdf_lattice* lattice);      /* 0 for a lattice without a band, for NULL, for a handle that is not alive */
+
 /* ---- force history: pressure/viscous force and moment of a body after every step, from the body's band only (src/Metrics.jl:116-195) --------
  * nds(body,x) is zero outside |d| ≤ 1, so the sums run over a list of ACTIVE TILES — boxes of 64×4×4 array cells (2-D: 64×4) with an interior cell at
  * d² ≤ 1, found by evaluating the body program on every interior cell, in ascending order, rebuilt only when the body changes.  One launch with one

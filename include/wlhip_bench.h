@@ -57,6 +57,10 @@ int wl_sim_counter(wl_sim* s, const char* name, long* out);
 /* the last wl_sdf_lattice_from_mesh of this process: exact (sample, element) closest-point tests made — the per-brick counts the kernel wrote, summed on the
  * host — and samples × elements; equal under WL_MESH_BRUTE */
 int wl_meshsdf_last_pairs(uint64_t* tested, uint64_t* total);
+/* the last mesh search of this process: bricks whose samples were searched (sweep 2) and bricks skipped because they lie wholly beyond the lattice's band
+ * (wlhip.h, band-limited baking) — searched + skipped = the brick count; skipped = 0 without a band and under WL_MESH_BRUTE.  With a band
+ * wl_meshsdf_last_pairs' `tested` counts candidates × live samples per searched brick, and per skipped brick the elements tested for its one sign sample */
+int wl_meshsdf_last_bricks(uint64_t* searched, uint64_t* skipped);
 /* wl_meshsdf_time(1): every later mesh bake of this process (wl_sdf_lattice_from_mesh, _from_moving_mesh, _update_mesh) fences its phases with stream
  * synchronisations and times them on the host; wl_meshsdf_last_times then gives the last bake's ms4 = {host tables, uploads, kernel, read-back}.  Off (the
  * default) nothing is fenced; ms4[0], which needs no fence, is recorded either way.  For tools/meshvel_bench.py. */

@@ -14,4 +14,4 @@ from .interp import advect_, interp, interp_  # noqa: F401
 from .simulation import (FusedSimulation, Simulation, measure_, pressure_force, pressure_moment, viscous_force,  # noqa: F401
                          viscous_moment)
 from . import bodies  # noqa: F401,E402
-from .bodies import Body, RigidMap, SdfLattice, SetBody, mesh_body, read_stl, setmap, weld  # noqa: F401,E402
+from .bodies import Body, RigidMap, SdfLattice, SetBody, mesh_band, mesh_body, read_stl, setmap, weld  # noqa: F401,E402

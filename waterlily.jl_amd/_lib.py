@@ -219,6 +219,10 @@ SIGNATURES = {
     "wl_sdf_lattice_set_velocity": (i32, [P, C.POINTER(f32), P]),
     "wl_sdf_lattice_read_velocity": (i32, [P, C.POINTER(f32), P]),
     "wl_sdf_lattice_has_velocity": (i32, [P]),
+    "wl_sdf_lattice_from_mesh_band": (i32, [C.POINTER(P), i32, C.POINTER(C.c_int32), C.POINTER(f32), f32, C.POINTER(f32), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                            C.POINTER(f32), f32, u32, P]),
+    "wl_sdf_lattice_band": (f32, [P]),
+    "wl_meshsdf_last_bricks": (i32, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "wl_meshsdf_time": (i32, [i32]),
     "wl_meshsdf_last_times": (i32, [C.POINTER(f64)]),
     "wl_sim_set_force_record": (i32, [P, C.POINTER(wl_bodyset), C.POINTER(f32), i32]),

@@ -171,13 +171,16 @@ class SdfLattice:
         self.id = int(lib().wl_sdf_lattice_id(h))
 
     @classmethod
-    def from_mesh(cls, vertices, elems, dims, origin=0, spacing=1, brute=False, vertex_velocity=None):
+    def from_mesh(cls, vertices, elems, dims, origin=0, spacing=1, brute=False, vertex_velocity=None, band=None):
         """the exact signed distance to a closed surface, sampled on the device (wl_sdf_lattice_from_mesh): `vertices` (nv × D) in the body frame, in flow-grid
         cells; `elems` (ne × 3) triangles in 3-D, (ne × 2) segments of closed polygons in 2-D, oriented outward (counter-clockwise seen from the fluid);
         sample i sits at origin + spacing·(i − ½), as for centres().  Negative inside.  brute=True tests every (sample, element) pair instead of culling: the
         same bits, for tests and timings.  A mesh that is open, non-manifold, unwelded (see weld) or oriented inward raises WlError with the reason.
         `vertex_velocity` (nv × D, body frame, cells per unit time) makes a DEFORMING body of it (wl_sdf_lattice_from_moving_mesh): the lattice also samples
-        the velocity of the closest surface point, the leaf adds it to V, and update_mesh / advance re-bake it in place as the vertices move."""
+        the velocity of the closest surface point, the leaf adds it to V, and update_mesh / advance re-bake it in place as the vertices move.
+        `band` (a positive number, flow-grid cells; wl_sdf_lattice_from_mesh_band) makes the lattice the full one clipped to ±band, with zero velocity samples
+        beyond it: the search skips the bricks wholly beyond the band, and every re-bake keeps the band.  measure! and the forces then also ask
+        band − |offset| > need + spacing·√D (mesh_band gives the smallest band with a quarter cell to spare).  band=None: today's call, today's bits."""
         v = np.ascontiguousarray(vertices, dtype=f32)
         e = np.ascontiguousarray(elems, dtype=np.int32)
         if v.ndim != 2 or v.shape[1] not in (2, 3) or e.ndim != 2 or e.shape[1] != v.shape[1]:
@@ -191,7 +194,12 @@ class SdfLattice:
         self.D, self.dims, self._h = D, dims, None
         h = C.c_void_p()
         fp = C.POINTER(C.c_float)
-        if vertex_velocity is None:
+        if band is not None:
+            wv = None if vertex_velocity is None else self._velocity_rows(vertex_velocity, v)
+            check(lib().wl_sdf_lattice_from_mesh_band(C.byref(h), D, (C.c_int32 * D)(*dims), o.ctypes.data_as(fp), float(spacing), v.ctypes.data_as(fp), len(v),
+                                                      e.ctypes.data_as(C.POINTER(C.c_int32)), len(e), None if wv is None else wv.ctypes.data_as(fp),
+                                                      float(band), 1 if brute else 0, None))
+        elif vertex_velocity is None:
             check(lib().wl_sdf_lattice_from_mesh(C.byref(h), D, (C.c_int32 * D)(*dims), o.ctypes.data_as(fp), float(spacing),
                                                  v.ctypes.data_as(fp), len(v), e.ctypes.data_as(C.POINTER(C.c_int32)), len(e), 1 if brute else 0, None))
         else:
@@ -215,6 +223,11 @@ class SdfLattice:
         if self._h is None:
             raise ValueError(f"SdfLattice.{who}: the lattice has been closed")
         return self._h
+
+    @property
+    def band(self):
+        """the band the lattice was made with (wl_sdf_lattice_band): 0.0 without one, or once the lattice is closed"""
+        return 0.0 if self._h is None else float(lib().wl_sdf_lattice_band(self._h))
 
     @property
     def has_velocity(self):
@@ -329,16 +342,25 @@ def mesh_placement(vertices, spacing=1.0, margin=5.0):
     return dims, tuple(float(lo[d] - margin - spacing / 2.0) for d in range(v.shape[1]))
 
 
-def mesh_body(vertices, elems, spacing=1.0, margin=None, offset=0.0, map=None, vertex_velocity=None):
+def mesh_band(eps=1.0, offset=0.0, spacing=1.0, D=3):
+    """the smallest band with a quarter cell to spare over the band rule of include/wlhip.h for measure! at ϵ = eps: 2 + eps + 1 + |offset| + spacing·√D + ¼"""
+    return 2.0 + float(eps) + 1.0 + abs(float(offset)) + float(spacing) * float(np.sqrt(float(D))) + 0.25
+
+
+def mesh_body(vertices, elems, spacing=1.0, margin=None, offset=0.0, map=None, vertex_velocity=None, band=None):
     """A closed triangle mesh (2-D: closed polygons of segments) as a body: its exact signed distance sampled at `spacing` into a lattice around its
     bounding box (SdfLattice.from_mesh, mesh_placement) and the lattice leaf over it — Body(("lattice", lat, origin, spacing, offset), map).  Vertices are
     in the body frame, in flow-grid cells; `map` places and moves the body.  The lattice every sample of which lies `margin` or more outside the box has
     edge_min ≥ margin; margin=None takes 5 + |offset|, which satisfies measure!'s rule edge_min − |offset| > 2 + ϵ + 1 at ϵ = 1 — a larger ϵ needs a
     larger margin (ϵ + 4 + |offset|).  The lattice is the body's: body.shape[1].close() frees it (at most LATTICE_MAX are alive).  With `vertex_velocity`
-    (nv × D) the body deforms: body.shape[1].advance(new_vertices, dt) re-bakes it in place each step — lay the lattice (margin) around every shape it takes."""
+    (nv × D) the body deforms: body.shape[1].advance(new_vertices, dt) re-bakes it in place each step — lay the lattice (margin) around every shape it takes.
+    `band`: a number is passed to from_mesh; True takes mesh_band(1.0, offset, spacing, D).  The margin default stays: edge_min is then min(margin-ish, band),
+    which the edge rule accepts whenever the band rule does."""
     margin = 5.0 + abs(float(offset)) if margin is None else float(margin)
     dims, origin = mesh_placement(vertices, float(spacing), margin)
-    lat = SdfLattice.from_mesh(vertices, elems, dims, origin, spacing, vertex_velocity=vertex_velocity)
+    if band is True:
+        band = mesh_band(1.0, offset, spacing, np.asarray(vertices).shape[1])
+    lat = SdfLattice.from_mesh(vertices, elems, dims, origin, spacing, vertex_velocity=vertex_velocity, band=band)
     return Body(("lattice", lat, origin, float(spacing), float(offset)), map)
 
 

@@ -49,7 +49,10 @@ struct MomArg { int on; float x0[3]; };      // on: moments about x0 (pressure_m
 // A validated wl_bodyset as the kernels take it (by value, kernarg memory): components beyond D zeroed, capsule axes normalised; depth = the deepest the stack gets
 // A WL_BODY_LATTICE leaf: node.h holds the BITS of its index into lat[] (an int32, read with __float_as_int: never arithmetic on it), m[0] = s; lat[] are the
 // nlat distinct lattices of the program as bodyset_prepare resolved them; lat_margin = min over its lattice leaves of edge_min − |R| (wlhip.h: out of range)
-struct SetArg { int32_t n; int32_t leaf_root; int32_t depth; int32_t nlat; float lat_margin; wl_body_node node[WL_BODYSET_MAX]; LatRef lat[WL_LATTICE_MAX]; };
+// band_left, band_cell: of the lattice leaves over BANDED lattices the one with the smallest band − |R| − s·√D, its band − |R| and its s·√D (s: the spacing the
+// lattice was baked at); band_left = ∞ when the program has none (wlhip.h: the band rule).  Host-side bookkeeping like lat_margin: no kernel reads them.
+struct SetArg { int32_t n; int32_t leaf_root; int32_t depth; int32_t nlat; float lat_margin; wl_body_node node[WL_BODYSET_MAX]; LatRef lat[WL_LATTICE_MAX];
+                float band_left; float band_cell; };
 static_assert(sizeof(SetArg) + 256 < 4096, "a kernel's arguments (the program and at most 256 bytes besides) must stay under 4 KB");
 namespace {
 __host__ __device__ __forceinline__ BodyArg body_arg(const wl_body_node& b) {
@@ -67,7 +70,8 @@ int bodyset_from_body(int D, const wl_body* b, SetArg* out);
 // A STORED program (the force recorder's band, the immediate force list) before a launch that uses it: every lattice it names is looked up again by id.
 // WL_EINVAL when one has been destroyed since — no kernel is ever launched with a freed pointer.  A program without lattice leaves: nothing to do.
 int bodyset_resolve(int D, SetArg* P);
-// the out-of-range rule of wlhip.h: WL_EINVAL unless every lattice leaf of P keeps edge_min − |R| > need (a program without lattice leaves passes)
+// the out-of-range rule of wlhip.h: WL_EINVAL unless every lattice leaf of P keeps edge_min − |R| > need (a program without lattice leaves passes) and every
+// leaf over a banded lattice band − |R| > need + s·√D; the message names the condition that failed and both numbers
 int bodyset_lattice_margin(const SetArg& P, float need, const char* who);
 int bodyset_measure_fields(float* sigma, float* mu0, float* mu1, float* V, const GridX& G, const SetArg& P, float eps, int exitBC, unsigned perdir, hipStream_t q);
 int bodyset_force_partials(int which, const float* a, float nu, const GridX& G, const SetArg& P, const float* x0, dim3 grid, double* part, hipStream_t q);

@@ -148,13 +148,17 @@ static int prepare_lattice_leaf(int D, const wl_body_node& a, wl_body_node& b, S
   const int id = (int)a.h;
   int32_t slot = 0;
   while (slot < out->nlat && out->lat[slot].id != id) slot++;
-  LatRef L; float edge = 0.f;
-  WL_TRY(wl::lattice_resolve(id, D, &L, &edge));
+  LatRef L; float edge = 0.f, band = 0.f, baked = 0.f;
+  WL_TRY(wl::lattice_resolve(id, D, &L, &edge, &band, &baked));
   if (slot == out->nlat) {
     WL_CHECK(slot < WL_LATTICE_MAX, "wl_bodyset: more than WL_LATTICE_MAX lattices in one program");      // (guard: no more than that many are alive)
     out->lat[slot] = L; out->nlat++;
   }
   out->lat_margin = std::fmin(out->lat_margin, edge - std::fabs(a.R));
+  if (band > 0.f) {      // a banded lattice (wlhip.h, band-limited baking): the leaf whose band − |R| − s·√D is smallest decides, s the spacing of the BAKE
+    const float left = band - std::fabs(a.R), cell = baked * sqrtf((float)D);
+    if (left - cell < out->band_left - out->band_cell) { out->band_left = left; out->band_cell = cell; }
+  }
   b.m[0] = a.m[0]; b.m[1] = b.m[2] = 0.f;
   static_assert(sizeof(slot) == sizeof(b.h), "the slot index travels as the bits of h");
   std::memcpy(&b.h, &slot, sizeof(slot));
@@ -167,7 +171,14 @@ int bodyset_resolve(int D, SetArg* P) {
   return 0;
 }
 int bodyset_lattice_margin(const SetArg& P, float need, const char* who) {
-  if (P.nlat == 0 || P.lat_margin > need) return 0;
+  const bool band_ok = P.nlat == 0 || P.band_left > need + P.band_cell;
+  if (band_ok && (P.nlat == 0 || P.lat_margin > need)) return 0;
+  if (P.lat_margin > need) {
+    wl_set_error(std::string(who) + ": a banded lattice leaf's band − |R| = " + std::to_string(P.band_left) + " is not above need + s·√D = " + std::to_string(need) +
+                 " + " + std::to_string(P.band_cell) + " = " + std::to_string(need + P.band_cell) +
+                 " — a cell that reads a clipped sample could miss the early exit (wlhip.h, band-limited baking: the band rule)");
+    return WL_EINVAL;
+  }
   wl_set_error(std::string(who) + ": a lattice leaf's edge_min − |R| = " + std::to_string(P.lat_margin) + " is not above " + std::to_string(need) +
                " — a cell outside the lattice's box could miss the early exit (wlhip.h, sampled bodies: out of range)");
   return WL_EINVAL;
@@ -176,7 +187,7 @@ int bodyset_prepare(int D, const wl_bodyset* s, SetArg* out) {
   WL_CHECK(D == 2 || D == 3, "bad dimension");
   WL_CHECK(s, "null wl_bodyset");
   WL_CHECK(s->n >= 1 && s->n <= WL_BODYSET_MAX, "wl_bodyset.n must be 1..WL_BODYSET_MAX");
-  *out = SetArg{}; out->lat_margin = INFINITY;
+  *out = SetArg{}; out->lat_margin = INFINITY; out->band_left = INFINITY; out->band_cell = 0.f;
   out->n = s->n;
   int sp = 0;
   for (int i = 0; i < s->n; i++) {
@@ -224,7 +235,7 @@ int bodyset_prepare(int D, const wl_bodyset* s, SetArg* out) {
 }
 int bodyset_from_body(int D, const wl_body* b, SetArg* out) {
   WL_CHECK(b && (b->kind == WL_BODY_SPHERE || b->kind == WL_BODY_PLANE), "wl_body.kind must be WL_BODY_SPHERE or WL_BODY_PLANE");
-  *out = SetArg{}; out->lat_margin = INFINITY;
+  *out = SetArg{}; out->lat_margin = INFINITY; out->band_left = INFINITY; out->band_cell = 0.f;
   out->n = 1; out->leaf_root = 1; out->depth = 1;
   wl_body_node& nd = out->node[0];
   nd.op = WL_OP_LEAF; nd.kind = b->kind; nd.R = b->R;

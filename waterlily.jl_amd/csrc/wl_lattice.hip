@@ -19,6 +19,8 @@ struct wl_sdf_lattice {
   float* w = nullptr; int32_t gen = 0;
   bool from_mesh = false; float origin[3] = {0.f, 0.f, 0.f}; float spacing = 0.f; int32_t nv = 0, ne = 0;
   std::vector<int32_t> elems; std::vector<float> verts;
+  std::vector<int32_t> adj;      // the topology of elems (MeshTables::adj), computed once at creation: a re-bake rebuilds the geometry tables only
+  float band = 0.f;              // > 0: made by wl_sdf_lattice_from_mesh_band — the samples are clip(d, −band, +band), every re-bake keeps it
 };
 
 namespace {
@@ -44,7 +46,7 @@ float edge_min_of(int D, const int32_t* n, const float* a) {
 }  // namespace
 
 namespace wl {
-int lattice_resolve(int id, int D, LatRef* out, float* edge_min) {
+int lattice_resolve(int id, int D, LatRef* out, float* edge_min, float* band, float* spacing) {
   std::lock_guard<std::mutex> lock(g_lat_mutex);
   for (const wl_sdf_lattice* L : g_lat)
     if (L && L->id == id) {
@@ -52,6 +54,8 @@ int lattice_resolve(int id, int D, LatRef* out, float* edge_min) {
       out->a = L->a; out->w = L->w; out->id = id; out->gen = L->gen;
       for (int q = 0; q < 3; q++) out->n[q] = L->n[q];
       *edge_min = L->edge_min;
+      if (band) *band = L->band;
+      if (spacing) *spacing = L->spacing;
       return 0;
     }
   wl_set_error("lattice id " + std::to_string(id) + " is unknown or has been destroyed (wl_sdf_lattice_create / _destroy)");
@@ -96,9 +100,11 @@ int wl_sdf_lattice_create(wl_sdf_lattice** out, int D, const int32_t* dims, cons
   *out = L;
   return 0;
 }
-// wl_sdf_lattice_from_mesh (host_velocity NULL) and wl_sdf_lattice_from_moving_mesh: `who` names the entry point in every refusal
+// wl_sdf_lattice_from_mesh (host_velocity NULL), wl_sdf_lattice_from_moving_mesh and wl_sdf_lattice_from_mesh_band (banded: `band` must be finite and
+// positive; else band = 0 and the search is the un-banded one): `who` names the entry point in every refusal
 static int lattice_from_mesh(const char* who_, wl_sdf_lattice** out, int D, const int32_t* dims, const float* host_origin, float spacing, const float* host_vertices,
-                             int32_t nv, const int32_t* host_elems, int32_t ne, const float* host_velocity, bool moving, unsigned flags, void* st) {
+                             int32_t nv, const int32_t* host_elems, int32_t ne, const float* host_velocity, bool moving, unsigned flags, void* st,
+                             bool banded = false, float band = 0.f) {
   const std::string who = who_;
   if (!out) { wl_set_error(who + ": null result"); return WL_EINVAL; }
   *out = nullptr;
@@ -115,6 +121,7 @@ static int lattice_from_mesh(const char* who_, wl_sdf_lattice** out, int D, cons
   if (!(std::isfinite(spacing) && spacing > 0.f)) { wl_set_error(who + ": the spacing must be finite and positive"); return WL_EINVAL; }
   for (int q = 0; q < D; q++)
     if (!std::isfinite(host_origin[q])) { wl_set_error(who + ": the origin is not finite"); return WL_EINVAL; }
+  if (banded && !(std::isfinite(band) && band > 0.f)) { wl_set_error(who + ": the band must be finite and positive"); return WL_EINVAL; }
   const auto t0 = std::chrono::steady_clock::now();
   wl::MeshTables tab;
   WL_TRY(wl::meshsdf_prepare(D, host_vertices, nv, host_elems, ne, &tab, who_));      // the refusals that concern the mesh; host only
@@ -133,7 +140,7 @@ static int lattice_from_mesh(const char* who_, wl_sdf_lattice** out, int D, cons
   if (e == hipSuccess && moving) e = hipMalloc((void**)&L->w, (size_t)D * count * sizeof(float));
   int rc = (int)e;
   if (e != hipSuccess) wl_set_error(who + ": " + hipGetErrorString(e));
-  else rc = wl::meshsdf_run(tab, L->n, host_origin, spacing, flags, L->a, host.data(), L->w, wl_stream(st));      // synchronises the stream, like create
+  else rc = wl::meshsdf_run(tab, L->n, host_origin, spacing, band, flags, L->a, host.data(), L->w, wl_stream(st));      // synchronises the stream, like create
   if (rc != 0) {
     if (L->a) (void)hipFree(L->a);
     if (L->w) (void)hipFree(L->w);
@@ -141,7 +148,8 @@ static int lattice_from_mesh(const char* who_, wl_sdf_lattice** out, int D, cons
     return rc;
   }
   L->edge_min = edge_min_of(D, L->n, host.data());
-  L->from_mesh = true; L->spacing = spacing; L->nv = nv; L->ne = ne;
+  L->from_mesh = true; L->spacing = spacing; L->nv = nv; L->ne = ne; L->band = band;
+  L->adj = std::move(tab.adj);
   for (int q = 0; q < D; q++) L->origin[q] = host_origin[q];
   L->elems.assign(host_elems, host_elems + (size_t)ne * D);
   L->verts.assign(host_vertices, host_vertices + (size_t)nv * D);
@@ -158,6 +166,17 @@ int wl_sdf_lattice_from_moving_mesh(wl_sdf_lattice** out, int D, const int32_t* 
                                     const int32_t* host_elems, int32_t ne, const float* host_vertex_velocity, unsigned flags, void* st) {
   return lattice_from_mesh("wl_sdf_lattice_from_moving_mesh", out, D, dims, host_origin, spacing, host_vertices, nv, host_elems, ne, host_vertex_velocity, true, flags, st);
 }
+int wl_sdf_lattice_from_mesh_band(wl_sdf_lattice** out, int D, const int32_t* dims, const float* host_origin, float spacing, const float* host_vertices, int32_t nv,
+                                  const int32_t* host_elems, int32_t ne, const float* host_vertex_velocity, float band, unsigned flags, void* st) {
+  return lattice_from_mesh("wl_sdf_lattice_from_mesh_band", out, D, dims, host_origin, spacing, host_vertices, nv, host_elems, ne, host_vertex_velocity,
+                           host_vertex_velocity != nullptr, flags, st, true, band);
+}
+float wl_sdf_lattice_band(const wl_sdf_lattice* L) {
+  if (!L) return 0.f;
+  std::lock_guard<std::mutex> lock(g_lat_mutex);
+  for (const wl_sdf_lattice* q : g_lat) if (q == L) return L->band;
+  return 0.f;
+}
 int wl_sdf_lattice_update_mesh(wl_sdf_lattice* L, const float* host_vertices, const float* host_vertex_velocity, unsigned flags, void* st) {
   const char* who = "wl_sdf_lattice_update_mesh";
   WL_CHECK(L && host_vertices, "wl_sdf_lattice_update_mesh: null lattice or vertices");
@@ -171,7 +190,8 @@ int wl_sdf_lattice_update_mesh(wl_sdf_lattice* L, const float* host_vertices, co
   const int D = L->D;
   const auto t0 = std::chrono::steady_clock::now();
   wl::MeshTables tab;
-  WL_TRY(wl::meshsdf_prepare(D, host_vertices, L->nv, L->elems.data(), L->ne, &tab, who));      // every mesh refusal, on the moved vertices; host only
+  // every mesh refusal that the moved vertices can meet (the connectivity passed at creation and is kept with its adjacency); host only
+  WL_TRY(wl::meshsdf_prepare_geometry(D, host_vertices, L->nv, L->elems.data(), L->ne, L->adj, &tab, who));
   if (L->w) {
     const std::vector<float> zeros(host_vertex_velocity ? 0 : (size_t)L->nv * D, 0.f);
     WL_TRY(wl::meshsdf_velocities(D, host_vertex_velocity ? host_vertex_velocity : zeros.data(), L->nv, L->elems.data(), L->ne, &tab, who));
@@ -180,7 +200,7 @@ int wl_sdf_lattice_update_mesh(wl_sdf_lattice* L, const float* host_vertices, co
   // from here on nothing is refused: the samples are overwritten in place, on the caller's stream — behind whatever that stream still reads them with
   const size_t count = (size_t)L->n[0] * (size_t)L->n[1] * (size_t)L->n[2];
   std::vector<float> host(count);
-  WL_TRY(wl::meshsdf_run(tab, L->n, L->origin, L->spacing, flags, L->a, host.data(), L->w, wl_stream(st)));
+  WL_TRY(wl::meshsdf_run(tab, L->n, L->origin, L->spacing, L->band, flags, L->a, host.data(), L->w, wl_stream(st)));
   L->edge_min = edge_min_of(D, L->n, host.data());
   L->verts.assign(host_vertices, host_vertices + (size_t)L->nv * D);
   L->gen++;

@@ -15,8 +15,8 @@ struct LatRef { const float* a; const float* w; int32_t n[3]; int32_t id; int32_
 
 namespace wl {
 // the live lattice `id` -> its samples and extents, and min|A| over the samples a clamped query reads (0: mixed signs there); WL_EINVAL for an unknown
-// or destroyed id
-int lattice_resolve(int id, int D, LatRef* out, float* edge_min);
+// or destroyed id.  band / spacing (either may be NULL): the band the lattice was made with (0: none) and the spacing it was baked at (0: not from a mesh)
+int lattice_resolve(int id, int D, LatRef* out, float* edge_min, float* band = nullptr, float* spacing = nullptr);
 }  // namespace wl
 
 #pragma clang fp contract(off)

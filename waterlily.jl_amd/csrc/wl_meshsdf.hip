@@ -24,8 +24,11 @@ struct MsArgs {
   int32_t ne; int32_t n[3]; int32_t nb[3]; long nbricks;
   float c[3]; float s; float rb; float slack; int brute;
   const float* wtab; float* w;      // VEL: the vertex velocities per element (ne×D×D, vertex-major like elem) and the D component planes they are extended into
+  float band;                       // BAND: the samples are clipped to ±band; a brick wholly beyond it is not searched (last: the offsets above stay what they were)
 };
+constexpr unsigned long long MS_SKIPPED = 1ull << 63;    // BAND: set in a brick's `pairs` entry when the brick was skipped (one sign search instead of sweep 2)
 unsigned long long g_ms_tested = 0, g_ms_total = 0;      // wl_meshsdf_last_pairs
+unsigned long long g_ms_searched = 0, g_ms_skipped = 0;  // wl_meshsdf_last_bricks
 double g_ms_ms[4] = {0, 0, 0, 0};                        // wl_meshsdf_last_times
 int g_ms_timed = 0;
 }  // namespace
@@ -109,7 +112,12 @@ __device__ __forceinline__ void ms_pair(const float* e, const float (&p)[2], flo
   d2 = r[0] * r[0] + r[1] * r[1];
 }
 
-template <int D, bool VEL>
+// BAND (a lattice made with a band b, wlhip.h band-limited baking): every sample stores clip(d, −b, +b).  Sweep 1 also forms the brick's lower bound
+// Lb = min_t(|c_b − c_t| − r_t) − r_b; a brick with Lb above b (plus the slack of the threshold, on the safe side) is FAR: it does not meet the surface, so
+// its samples share one sign and all of them are clipped.  A far wave finds that sign by searching for its first sample alone, in parallel over the
+// elements: each lane walks its own elements in ascending index with a strict <, a wave reduction then takes the smallest d² and, on equal d², the smallest
+// index — the winner of the serial walk, with its bits.  Far and near waves of a workgroup walk the same chunk loop: the barriers are those of BAND = false.
+template <int D, bool VEL, bool BAND>
 __global__ __launch_bounds__(256) void k_meshsdf(const MsArgs A) {
   constexpr int NE = D * D, NR = D == 3 ? 7 : 3;
   constexpr int EXT[3] = {4, D == 3 ? 4 : 16, D == 3 ? 4 : 1};
@@ -138,18 +146,40 @@ __global__ __launch_bounds__(256) void k_meshsdf(const MsArgs A) {
   }
   // sweep 1: the upper bound of the brick, over the spheres alone (global memory, every lane its own elements)
   float thresh = INFINITY;
+  bool far = false;                                        // BAND: the whole brick lies beyond the band (the same value in every lane)
+  float p0[D];                                             // BAND: the brick's first sample, lane 0's p in every lane
   if (!A.brute && wave_on) {
-    float m = INFINITY;
+    float m = INFINITY, lo = INFINITY;
     for (int t = lane; t < A.ne; t += 64) {
       const float4 q = A.sph[t];
       float dd = (q.x - cb[0]) * (q.x - cb[0]) + (q.y - cb[1]) * (q.y - cb[1]);
       if (D == 3) dd = dd + (q.z - cb[D - 1]) * (q.z - cb[D - 1]);
       m = fminf(m, sqrtf(dd) + q.w);
+      if constexpr (BAND) lo = fminf(lo, sqrtf(dd) - q.w);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o, 64));
     const float ub = m + A.rb;
     thresh = ub + (ub * 1e-4f + A.slack);
+    if constexpr (BAND) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) lo = fminf(lo, __shfl_xor(lo, o, 64));
+      far = lo - A.rb > A.band + (A.band * 1e-4f + A.slack);
+      if (far) {                                           // the first sample's own bound (r_b = 0): what the sign search culls with
+#pragma unroll
+        for (int d = 0; d < D; d++) p0[d] = A.c[d] + A.s * ((float)i0[d] - 0.5f);
+        float mp = INFINITY;
+        for (int t = lane; t < A.ne; t += 64) {
+          const float4 q = A.sph[t];
+          float dd = (q.x - p0[0]) * (q.x - p0[0]) + (q.y - p0[1]) * (q.y - p0[1]);
+          if (D == 3) dd = dd + (q.z - p0[D - 1]) * (q.z - p0[D - 1]);
+          mp = fminf(mp, sqrtf(dd) + q.w);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mp = fminf(mp, __shfl_xor(mp, o, 64));
+        thresh = mp + (mp * 1e-4f + A.slack);
+      }
+    }
   }
   // sweep 2: the candidates of each staged chunk, exactly
   float best = INFINITY, br[D];
@@ -169,6 +199,33 @@ __global__ __launch_bounds__(256) void k_meshsdf(const MsArgs A) {
     __syncthreads();
     if (!wave_on) continue;                                // (no barrier below: the loop bounds are the same for every wave)
     const int cnt = min(MS_CHUNK, A.ne - base);
+    if constexpr (BAND) {
+      if (far) {                                           // the sign search: one point, every lane its own element of each 64-group
+        for (int k = 0; k < cnt; k += 64) {
+          const int j = k + lane;
+          bool cand = j < cnt;
+          if (cand) {
+            const float4 q = s_s[j];
+            float dd = (q.x - p0[0]) * (q.x - p0[0]) + (q.y - p0[1]) * (q.y - p0[1]);
+            if (D == 3) dd = dd + (q.z - p0[D - 1]) * (q.z - p0[D - 1]);
+            cand = sqrtf(dd) - q.w <= thresh;
+          }
+          const unsigned long long mask = __ballot(cand);
+          if (!mask) continue;                             // a 64-group without a candidate is skipped as a whole
+          ntest += (unsigned long long)__popcll(mask);
+          if (cand) {
+            float d2, r[D], pv = 0.f, pw = 0.f; int reg;
+            ms_pair<false>(&s_e[j * NE], p0, d2, reg, r, pv, pw);
+            if (d2 < best) {
+              best = d2; bt = base + j; breg = reg;
+#pragma unroll
+              for (int d = 0; d < D; d++) br[d] = r[d];
+            }
+          }
+        }
+        continue;
+      }
+    }
     for (int k = 0; k < cnt; k += 64) {
       const int j = k + lane;
       bool cand = j < cnt;
@@ -194,6 +251,38 @@ __global__ __launch_bounds__(256) void k_meshsdf(const MsArgs A) {
       }
     }
   }
+  if constexpr (BAND) {
+    if (far) {
+      // the first of the smallest d² over the lanes: (d², index) in lexicographic order — an element belongs to one lane only (index ≡ lane mod 64)
+      float md = best; int mt = best < INFINITY ? bt : 0x7fffffff;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float od = __shfl_xor(md, o, 64); const int ot = __shfl_xor(mt, o, 64);
+        if (od < md || (od == md && ot < mt)) { md = od; mt = ot; }
+      }
+      const unsigned long long wm = __ballot(best == md && bt == mt);
+      const int src = wm ? __ffsll((long long)wm) - 1 : 0;
+      if (!wm) mt = 0;                                     // (guard: the element that attains the point's bound is always a candidate)
+      const int wreg = __shfl(breg, src, 64);
+      float wr[D];
+#pragma unroll
+      for (int d = 0; d < D; d++) wr[d] = __shfl(br[d], src, 64);
+      if (lane == 0) A.pairs[brick] = ntest | MS_SKIPPED;
+      if (live) {
+        const float* nn = A.nrm + ((size_t)mt * NR + wreg) * D;
+        float sg = wr[0] * nn[0] + wr[1] * nn[1];
+        if (D == 3) sg = sg + wr[D - 1] * nn[D - 1];
+        const size_t o = (size_t)i[0] + (size_t)A.n[0] * ((size_t)i[1] + (size_t)A.n[1] * (size_t)i[2]);
+        A.a[o] = sg < 0.f ? -A.band : A.band;
+        if constexpr (VEL) {
+          const size_t plane = (size_t)A.n[0] * (size_t)A.n[1] * (size_t)A.n[2];
+#pragma unroll
+          for (int c = 0; c < D; c++) A.w[(size_t)c * plane + o] = 0.f;
+        }
+      }
+      return;                                              // (no barrier below)
+    }
+  }
   const unsigned long long nlive = (unsigned long long)__popcll(__ballot(live));
   if (wave_on && lane == 0) A.pairs[brick] = ntest * nlive;
   if (live) {
@@ -202,6 +291,17 @@ __global__ __launch_bounds__(256) void k_meshsdf(const MsArgs A) {
     if (D == 3) sg = sg + br[D - 1] * nn[D - 1];
     const float d = sqrtf(best);
     const size_t o = (size_t)i[0] + (size_t)A.n[0] * ((size_t)i[1] + (size_t)A.n[1] * (size_t)i[2]);
+    if constexpr (BAND) {
+      if (d > A.band) {                                    // the clip: ±band with the sign of the full value, no velocity beyond the band
+        A.a[o] = sg < 0.f ? -A.band : A.band;
+        if constexpr (VEL) {
+          const size_t plane = (size_t)A.n[0] * (size_t)A.n[1] * (size_t)A.n[2];
+#pragma unroll
+          for (int c = 0; c < D; c++) A.w[(size_t)c * plane + o] = 0.f;
+        }
+        return;
+      }
+    }
     A.a[o] = sg < 0.f ? -d : d;                            // d = 0 has p = q, sg = ±0: +0 is stored
     if constexpr (VEL) {                                   // the closest-point extension of the vertex velocities: W = wa + v·(wb − wa) + w·(wc − wa), gathered once
       const float* wt = A.wtab + (size_t)bt * NE;
@@ -250,7 +350,10 @@ void bounding_sphere(const V3* p, int k, V3* c, double* r) {
 }  // namespace
 
 namespace wl {
-int meshsdf_prepare(int D, const float* v, int32_t nv, const int32_t* e, int32_t ne, MeshTables* out, const char* who) {
+// One body for both entry points, so that everything that is rounded comes from the same statements in the same order.  topo NULL: the call of a lattice's
+// creation — every refusal in the documented order, the adjacency built (and left in out->adj).  topo given (the adjacency kept since creation, for the same
+// e): the index checks, the edge map and the 2-D in/out tables are skipped — they depend on the connectivity alone and have passed.
+static int prepare_tables(int D, const float* v, int32_t nv, const int32_t* e, int32_t ne, const std::vector<int32_t>* topo, MeshTables* out, const char* who) {
   const std::string F = std::string(who) + ": ";
   if (D == 3 ? (nv < 4 || ne < 4) : (nv < 3 || ne < 3)) {
     wl_set_error(F + (D == 3 ? "a closed surface has at least 4 vertices and 4 triangles" : "a closed polygon has at least 3 vertices and 3 segments"));
@@ -261,7 +364,7 @@ int meshsdf_prepare(int D, const float* v, int32_t nv, const int32_t* e, int32_t
     if (!std::isfinite(v[q])) { wl_set_error(F + "vertex " + std::to_string(q / D) + " is not finite"); return WL_EINVAL; }
     scale = std::fmax(scale, std::fabs((double)v[q]));
   }
-  for (size_t q = 0; q < (size_t)ne * D; q++)
+  for (size_t q = 0; !topo && q < (size_t)ne * D; q++)
     if (e[q] < 0 || e[q] >= nv) { wl_set_error(F + "element " + std::to_string(q / D) + " names index " + std::to_string(e[q]) + " outside [0, nv)"); return WL_EINVAL; }
   auto P = [&](int32_t i) { return V3{v[(size_t)i * D], v[(size_t)i * D + 1], D == 3 ? v[(size_t)i * D + 2] : 0.0}; };
   const int NR = D == 3 ? 7 : 3;
@@ -279,8 +382,12 @@ int meshsdf_prepare(int D, const float* v, int32_t nv, const int32_t* e, int32_t
       nf[t] = V3{d.y / l, -d.x / l, 0.0};                  // outward of a counter-clockwise polygon
     }
   }
-  std::vector<int32_t> adj((size_t)ne * D, -1);             // 3-D: the triangle across edge k; 2-D: the segment into A (k = 0) / out of B (k = 1)
-  if (D == 3) {
+  std::vector<int32_t> built;                               // 3-D: the triangle across edge k; 2-D: the segment into A (k = 0) / out of B (k = 1)
+  if (!topo) built.assign((size_t)ne * D, -1);
+  const std::vector<int32_t>& adj = topo ? *topo : built;
+  if (topo) {
+    WL_CHECK(topo->size() == (size_t)ne * D, "mesh tables: the kept adjacency does not belong to this connectivity");
+  } else if (D == 3) {
     const std::string why = " is not shared by exactly two triangles in opposite directions: the surface is open, non-manifold or not oriented alike — "
                             "weld coincident vertices (unwelded triangle soup fails here) and give every triangle the same orientation";
     std::unordered_map<uint64_t, int32_t> dir;
@@ -295,7 +402,7 @@ int meshsdf_prepare(int D, const float* v, int32_t nv, const int32_t* e, int32_t
         const int32_t i = e[3 * t + k], j = e[3 * t + (k + 1) % 3];
         const auto it = dir.find(ekey(j, i));
         if (it == dir.end()) { wl_set_error(F + "edge (" + std::to_string(i) + ", " + std::to_string(j) + ")" + why); return WL_EINVAL; }
-        adj[(size_t)3 * t + k] = it->second;
+        built[(size_t)3 * t + k] = it->second;
       }
   } else {
     std::vector<int32_t> in(nv, -1), og(nv, -1);
@@ -307,7 +414,7 @@ int meshsdf_prepare(int D, const float* v, int32_t nv, const int32_t* e, int32_t
                      " outgoing segments, a closed polygon has exactly one incoming and one outgoing at every vertex (open or branching polyline; weld coincident vertices)");
         return WL_EINVAL;
       }
-    for (int32_t t = 0; t < ne; t++) { adj[(size_t)2 * t] = in[e[2 * t]]; adj[(size_t)2 * t + 1] = og[e[2 * t + 1]]; }
+    for (int32_t t = 0; t < ne; t++) { built[(size_t)2 * t] = in[e[2 * t]]; built[(size_t)2 * t + 1] = og[e[2 * t + 1]]; }
   }
   double vol = 0;
   for (int32_t t = 0; t < ne; t++)
@@ -351,7 +458,14 @@ int meshsdf_prepare(int D, const float* v, int32_t nv, const int32_t* e, int32_t
       if (D == 3) n[2] = (float)rows[q].z;
     }
   }
+  if (!topo) out->adj = std::move(built);
   return 0;
+}
+int meshsdf_prepare(int D, const float* v, int32_t nv, const int32_t* e, int32_t ne, MeshTables* out, const char* who) {
+  return prepare_tables(D, v, nv, e, ne, nullptr, out, who);
+}
+int meshsdf_prepare_geometry(int D, const float* v, int32_t nv, const int32_t* e, int32_t ne, const std::vector<int32_t>& adj, MeshTables* out, const char* who) {
+  return prepare_tables(D, v, nv, e, ne, &adj, out, who);
 }
 
 int meshsdf_velocities(int D, const float* w, int32_t nv, const int32_t* e, int32_t ne, MeshTables* out, const char* who) {
@@ -364,7 +478,7 @@ int meshsdf_velocities(int D, const float* w, int32_t nv, const int32_t* e, int3
   return 0;
 }
 
-int meshsdf_run(const MeshTables& m, const int32_t* n, const float* c, float s, unsigned flags, float* a_dev, float* a_host, float* w_dev, hipStream_t st) {
+int meshsdf_run(const MeshTables& m, const int32_t* n, const float* c, float s, float band, unsigned flags, float* a_dev, float* a_host, float* w_dev, hipStream_t st) {
   const int D = m.D;
   const bool vel = w_dev != nullptr;
   WL_CHECK(!vel || m.wtab.size() == m.elem.size(), "mesh search: velocity samples asked for without a velocity table");
@@ -379,7 +493,7 @@ int meshsdf_run(const MeshTables& m, const int32_t* n, const float* c, float s, 
     return 0;
   };
   MsArgs A{};
-  A.ne = m.ne; A.s = s; A.brute = (flags & WL_MESH_BRUTE) ? 1 : 0;
+  A.ne = m.ne; A.s = s; A.brute = (flags & WL_MESH_BRUTE) ? 1 : 0; A.band = band;
   const int ext[3] = {4, D == 3 ? 4 : 16, D == 3 ? 4 : 1};
   double scale = std::fmax(m.scale, std::fabs((double)s));
   size_t count = 1;
@@ -411,8 +525,15 @@ int meshsdf_run(const MeshTables& m, const int32_t* n, const float* c, float s, 
   WL_HIP(hipMemcpyAsync((void*)A.nrm, m.nrm.data(), m.nrm.size() * 4, hipMemcpyHostToDevice, st));
   if (vel) WL_HIP(hipMemcpyAsync((void*)A.wtab, m.wtab.data(), m.wtab.size() * 4, hipMemcpyHostToDevice, st));
   WL_TRY(lap(1));
-  if (D == 3) { if (vel) hipLaunchKernelGGL((k_meshsdf<3, true>), dim3((unsigned)nblocks), dim3(256), 0, st, A); else hipLaunchKernelGGL((k_meshsdf<3, false>), dim3((unsigned)nblocks), dim3(256), 0, st, A); }
-  else { if (vel) hipLaunchKernelGGL((k_meshsdf<2, true>), dim3((unsigned)nblocks), dim3(256), 0, st, A); else hipLaunchKernelGGL((k_meshsdf<2, false>), dim3((unsigned)nblocks), dim3(256), 0, st, A); }
+#define MS_LAUNCH(D_, V_, B_) hipLaunchKernelGGL((k_meshsdf<D_, V_, B_>), dim3((unsigned)nblocks), dim3(256), 0, st, A)
+  if (band > 0.f) {      // a lattice with a band: its own instantiations
+    if (D == 3) { if (vel) MS_LAUNCH(3, true, true); else MS_LAUNCH(3, false, true); }
+    else { if (vel) MS_LAUNCH(2, true, true); else MS_LAUNCH(2, false, true); }
+  } else {
+    if (D == 3) { if (vel) MS_LAUNCH(3, true, false); else MS_LAUNCH(3, false, false); }
+    else { if (vel) MS_LAUNCH(2, true, false); else MS_LAUNCH(2, false, false); }
+  }
+#undef MS_LAUNCH
   WL_LAUNCH_CHECK();
   WL_TRY(lap(2));
   std::vector<unsigned long long> pairs((size_t)A.nbricks);
@@ -420,8 +541,9 @@ int meshsdf_run(const MeshTables& m, const int32_t* n, const float* c, float s, 
   WL_HIP(hipMemcpyAsync(pairs.data(), A.pairs, pairs.size() * 8, hipMemcpyDeviceToHost, st));
   WL_HIP(hipStreamSynchronize(st));
   WL_TRY(lap(3));
-  unsigned long long tested = 0;
-  for (unsigned long long q : pairs) tested += q;
+  unsigned long long tested = 0, skipped = 0;
+  for (unsigned long long q : pairs) { tested += q & ~MS_SKIPPED; skipped += q >> 63; }
+  g_ms_searched = (unsigned long long)A.nbricks - skipped; g_ms_skipped = skipped;
   g_ms_tested = tested; g_ms_total = (unsigned long long)count * (unsigned long long)m.ne;
   return 0;
 }
@@ -432,6 +554,11 @@ void wl::meshsdf_note_tables_ms(double ms) { g_ms_ms[0] = ms; }
 extern "C" int wl_meshsdf_last_times(double* ms4) {
   WL_CHECK(ms4, "wl_meshsdf_last_times: null result");
   for (int q = 0; q < 4; q++) ms4[q] = g_ms_ms[q];
+  return 0;
+}
+extern "C" int wl_meshsdf_last_bricks(uint64_t* searched, uint64_t* skipped) {
+  WL_CHECK(searched && skipped, "wl_meshsdf_last_bricks: null result");
+  *searched = g_ms_searched; *skipped = g_ms_skipped;
   return 0;
 }
 extern "C" int wl_meshsdf_last_pairs(uint64_t* tested, uint64_t* total) {
