@@ -263,7 +263,7 @@ int wl_sim_init_flow(wl_sim* s, void* stream);          /* BC!(u), u⁰=u, μ₀
        stores.  Not with the sgs model, forcing, a body, slabs, exitBC, a periodic direction or "store_f".  The pressure may end a call in the other of the handle's
        two pressure arrays: wl_sim_field("p") reports the one that holds it; a caller-owned p always receives it (there a single step stores both times).
    "tailwide"[1] the two projection tails run with four x-adjacent cells per thread and 16-byte loads and stores, the plane's x staged through LDS (k_project_wide,
-       wl_poisson.hip): the same statements per cell, the same launches, identical bits.  Where the pair tails run (3-D, constant coefficients, even nx) and,
+       wl_project.hip): the same statements per cell, the same launches, identical bits.  Where the pair tails run (3-D, constant coefficients, even nx) and,
        in addition, nx·ny is a multiple of 4, nx ≥ 8 and every array of the launch starts on a 16-byte boundary; anything else — and "tailwide" 0 — runs the
        one- and two-cell kernels as before.
    "convf"[1] the tiled conv_diff!+BDIM! evaluates every face flux once (wl_convf.hip); 0: the two-cells-per-thread kernel that re-evaluates upper faces

@@ -87,12 +87,12 @@ conv_march_ok = _gate("conv_march_ok", "wl_convm.hip", ["g.cs < (1L << 30) && g.
                       'the z-marching conv_diff! ("convm" = 1, where the tiled kernel does not run): nx ≥ 8, ny ≥ 8')
 conv_z_ok = _gate("conv_z_ok", "wl_convz.hip", ["per == 0 && g.nx >= 34 && g.ny >= 18 && g.cs < (1L << 30)"], lambda g: g[0] >= 34 and g[1] >= 18,
                   'the flux-once z-marching conv_diff! ("convz" = 1): nx ≥ 34, ny ≥ 18')
-project_wide_path = _gate("project_wide_path", "wl_poisson.hip",
+project_wide_path = _gate("project_wide_path", "wl_project.hip",
                           ["(g.nx & 1) == 0 && g.nx >= 8 && g.ny >= 4 && (g.sz & 3) == 0 && g.k0 >= 1 && g.k1 <= g.nz - 1", "if (tw_lds_bytes(g) > 48 * 1024 || (long)tw_nb8(g) * g.nz > 0x7fffffffL) return false;",
                            "return (size_t)(WL_TW_CHUNK + 2 * g.sy + 8) * sizeof(float); }", "#define WL_TW_CHUNK (4 * WL_BLOCK)"],
                           lambda g: g[0] % 2 == 0 and g[0] >= 8 and g[1] >= 4 and (g[0] * g[1]) % 4 == 0 and (1024 + 2 * g[0] + 8) * 4 <= 48 * 1024,
                           "the four-cells-per-thread projection tails: even nx ≥ 8, ny ≥ 4, nx·ny a multiple of 4, staged window (2·nx + 1032 floats) within 48 KiB of LDS")
-fold_ok = _gate("fold_ok", "wl_sim.hip", ["G.nz == G.gnz && G.nx >= 6 && G.ny >= 6 && G.nz >= 6"], lambda g: min(g) >= 6, "BC! folded into the producer's stores: every side ≥ 6")
+fold_ok = _gate("fold_ok", "wl_bcfold.hpp", ["g.nz == g.gnz && g.nx >= 6 && g.ny >= 6 && g.nz >= 6"], lambda g: min(g) >= 6, "BC! folded into the producer's stores: every side ≥ 6")
 tail_cells_ok = _gate("tail_ok", "wl_mg.hip", ["if (lv[(size_t)first].g.D != 3 || lv[(size_t)first].x_.cs > WL_TAIL_CELLS) return false;", "(int)lv.size() - first > WL_TAIL_MAXLV"],
                       lambda g: cells(g) <= WL_TAIL_CELLS, "the rest of the V-cycle in one launch from the first level of at most 8192 cells")
 const_L_ok = _gate("check_const_L", "wl_poisson.hip", ["if (g.nx < 4 || g.ny < 4 || (g.D == 3 && (g.k1 - g.k0) < 1)) return 0;"], lambda g: g[0] >= 4 and g[1] >= 4 and g[2] >= 4,

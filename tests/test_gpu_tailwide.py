@@ -1,4 +1,4 @@
-"""The projection tails with four cells per thread and 16-byte accesses (option "tailwide", k_project_wide in csrc/wl_poisson.hip): the statements per cell are
+"""The projection tails with four cells per thread and 16-byte accesses (option "tailwide", k_project_wide in csrc/wl_project.hip): the statements per cell are
 those of the one- and two-cell kernels, so a handle with tailwide=1 against a handle with tailwide=0 on the same library must agree on u, u⁰, p on every cell
 (ghosts, edges, corners) as raw bits, on pois.n and on the Δt history, with the same number of launches per call — over the shapes that put the row seam inside
 and outside a quad, enough blocks for the slots of the encoded maximum to wrap, the speculation switched off piecewise, folded and deferred BC! with a nonzero U on

@@ -9,6 +9,10 @@
 #pragma once
 #include "wl_common.hpp"
 
+// the grids the stores below are written for: a 3-D single domain (global = local) on which the two wall layers of a direction belong to different cells.
+// Every producer that folds asks this; what else it needs (whole launch, scheme, the handle's switches) it adds itself
+static inline bool wl_bc_fold_geom_ok(const GridX& g) { return g.D == 3 && g.nz == g.gnz && g.nx >= 6 && g.ny >= 6 && g.nz >= 6; }
+
 #ifdef __HIPCC__
 // uo: the (3-component) output array; (i,j,k): LOCAL 0-based coordinates of an INTERIOR cell (single domain: global = local);
 // v: the three components the producer computed for it.  Returns after storing the cell and the ghost locations it owns.

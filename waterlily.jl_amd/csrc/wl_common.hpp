@@ -243,21 +243,14 @@ struct ProfScope {   // RAII: records start at construction and stop at destruct
   ~ProfScope();
 };
 
-// BC!(u,U) for a tuple U folded into a producer's stores (wl_bcfold.hpp): request (on = 1, U) / report (on = 1 if it was applied)
+// conv_diff!+BDIM! launches (conv_diff_bdim): BC!(u,U) for a tuple U folded into the producer's stores (wl_bcfold.hpp) — request (on = 1, U) / report (on = 1 if it
+// was applied) — and what else the time-step path hands that launch.  (The projection tails have their own request and report: wl_project.hpp)
 struct BcFold { int on; float U[3];
                 // in: x of a projection whose velocity update was deferred to this conv_diff! launch (wl_convf.hip, PROJ); out: 1 = the launch applied it
                 const float* proj_x = nullptr; int proj_done = 0;
-                // in: BC!(u_in,U) was deferred — the producer of u_in wrote the interior only (wl_sim, mom_step!): the tail reads the wall-normal boundary faces as U
-                int usub = 0;
-                // in: device flag — the tail kernel does nothing unless *go > 0 (the solver's convergence decision taken on the device: wl::decide_converged; the tail is
-                // queued behind the V-cycle before the host has read the norms)
-                const float* go = nullptr;
-                // in (conv_diff!+BDIM! launches): Δt is read from this device location instead of the argument (wl_sim_mom_steps: the next step's predictor is queued
-                // before the host has read the CFL maximum); honoured by the flux-once tiled kernel only
-                const float* dt_dev = nullptr;
-                // in (projection tails): 1 = take the four-cells-per-thread form where the shape and the arrays allow it (wl_sim, option "tailwide");
-                // out: the launcher that took it sets *wide_ran = 1 (host location, optional)
-                int wide = 0; int* wide_ran = nullptr; };
+                // in: Δt is read from this device location instead of the argument (wl_sim_mom_steps: the next step's predictor is queued before the host has read
+                // the CFL maximum); honoured by the flux-once tiled kernel only
+                const float* dt_dev = nullptr; };
 
 // ---- kernel launchers shared between the leaf C ABI and the composite handles --------------------
 namespace wl {
@@ -371,13 +364,7 @@ bool resjac_ok(const GridX& g, const ConstL& cl);
 int resjac(float* xout, float* rout, const float* x, const float* u, const GridX& g, float dt, float w, const ConstL& cl, const RedWs& ws, int slot_d, int slot_f, hipStream_t s,
            bool shell = true, const float* bcU = nullptr);   // shell = false: x's (and x_out's) ghost cells are known to be +0 — the ghost-shell scaling pass is skipped
 int shell_nonzero(const float* a, const GridX& g, int* dev_flag, hipStream_t s);
-int project_unscale(float* u, const float* L, const float* x, float* pout, const GridX& g, float dt, const ConstL& cl, hipStream_t s, const BcFold* fold = nullptr);
 int decide_converged(const RedWs& ws, double r1tol, double rinftol, double ninside, int check_head, int slot_d, int slot_f, int out_slot, hipStream_t s);   // res_f[out_slot] = 1 converged / 0 iterate / −1 the fused head's mean shift is due: solver!'s break test on the device
-bool project_cfl_pair_path(const GridX& g, const ConstL& cl);   // the two-cells-per-thread tail will run (the form that honours BcFold::usub)
-int project_cfl(float* uout, const float* uin, const float* L, const float* x, float* pout, float* sigma, const GridX& g, float dt, const ConstL& cl, const RedWs& ws, int slot_f, hipStream_t s, int store_sigma = 1, const BcFold* fold = nullptr);
-int project_unscale_split(float* u, const float* L, const float* x, float* pout, const GridX& g, float dt, const ConstL& near, const ConstL& far, int na, int nb, hipStream_t s);
-int project_cfl_split(float* uout, const float* uin, const float* L, const float* x, float* pout, float* sigma, const GridX& g, float dt, const ConstL& near, const ConstL& far,
-                      int na, int nb, const RedWs& ws, int slot_f, hipStream_t s, int store_sigma = 1);
 // computes L₁/L∞ of r into ws.res_d[slot_d], ws.res_f[slot_f] (device) — ghosts of r are zero by construction
 int norms_dev(const float* r, const GridX& g, const RedWs& ws, int slot_d, int slot_f, hipStream_t s);
 int increment(float* r, float* x, const float* eps, const float* L, const float* D, const GridX& g, float w, hipStream_t s);

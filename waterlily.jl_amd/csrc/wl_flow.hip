@@ -738,7 +738,7 @@ static int conv_diff_launch2(float* r, const float* u, float* Phi, const GridX& 
     // BC!(u_out,U) folded into the producer (wl_bcfold.hpp) when this launch covers the whole single domain: x/y in the wall tiles'
     // stores, the z ghost planes by one small launch — the caller then skips k_bc_vec (fold->on reports what happened)
     BdimArgs bt = *bd;
-    const bool foldok = fold && fold->on && SCH != WL_VANLEER && g.nz == g.gnz && own_a == g.k0 && own_b == g.k1 && g.nx >= 6 && g.ny >= 6 && g.nz >= 6;
+    const bool foldok = fold && fold->on && SCH != WL_VANLEER && wl_bc_fold_geom_ok(g) && own_a == g.k0 && own_b == g.k1;
     bt.bc_on = foldok ? 1 : 0;
     if (foldok) for (int c = 0; c < 3; c++) bt.bcU[c] = fold->U[c];
     if (fold && fold->proj_x) {   // mom_project!'s deferred tail: the kernel reads u through u −= L∇x and BC!(u,U) (wl_convf.hip, PROJ; the caller checked conv_proj_ok)

@@ -15,9 +15,5 @@ namespace wl {
 // the fused head on a scaled pressure whose `./= dt_prev` is pending (dt_prev = 0: x is an unscaled p — wl_common.hpp's resjac)
 int resjac(float* xout, float* rout, const float* x, const float* u, const GridX& g, float dt, float w, const ConstL& cl, const RedWs& ws, int slot_d, int slot_f, hipStream_t s,
            bool shell, const float* bcU, float dt_prev);
-// the default projection tails with skip_p: p_out = x/dt is not stored (and p_out not touched).  The forms that have the switch: k_project_unscale on 3-D
-// constant-coefficient levels, k_project_unscale2, k_project_cfl2 — any other form asked to skip is an error, not a silent store
-int project_unscale(float* u, const float* L, const float* x, float* pout, const GridX& g, float dt, const ConstL& cl, hipStream_t s, const BcFold* fold, bool skip_p);
-int project_cfl(float* uout, const float* uin, const float* L, const float* x, float* pout, float* sigma, const GridX& g, float dt, const ConstL& cl, const RedWs& ws, int slot_f, hipStream_t s,
-                int store_sigma, const BcFold* fold, bool skip_p);
+// (the tails that leave the store out: TailReq::skip_p, wl_project.hpp — k_project_unscale on 3-D constant-coefficient levels, k_project_cfl2, k_project_wide)
 }  // namespace wl

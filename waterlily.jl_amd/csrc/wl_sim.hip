@@ -10,6 +10,7 @@
 #include "wl_mg.hpp"
 #include "wl_body.hpp"
 #include "wl_pdefer.hpp"
+#include "wl_project.hpp"
 #include "wl_forces.hpp"
 #include "wl_meanflow.hpp"
 #include "wl_observe.hpp"
@@ -100,8 +101,7 @@ struct wl_sim {
   // measured at 512³: projection tails −0.04 ms/step (kept), tiled conv_diff! +0.2…0.4 ms/step — the ghost writes are sector-granular
   // wherever they happen, and inside the tiled kernel they sit on the wall tiles' critical path (off; `bcfold` = 3 turns it on)
   int use_bcfold = 1;         // bit 0: projection tails, bit 1: tiled conv_diff!+BDIM!
-  bool fold_ok(int bit) const { return (use_bcfold & bit) && d.D == 3 && !comm && !d.exitBC && !d.perdir_mask && G.nz == G.gnz && G.nx >= 6 && G.ny >= 6 && G.nz >= 6; }
-  BcFold fold_req(int bit) const { BcFold f{fold_ok(bit) ? 1 : 0, {d.uBC[0], d.uBC[1], d.uBC[2]}}; return f; }
+  bool fold_ok(int bit) const { return (use_bcfold & bit) && !comm && !d.exitBC && !d.perdir_mask && wl_bc_fold_geom_ok(G); }
   int bc_u(hipStream_t s) {
     WL_TRY(sync_u(s));
     if (df.bc_folded) { df.bc_folded = false; return 0; }      // the producer already wrote every boundary location
@@ -124,7 +124,7 @@ struct wl_sim {
       return wl::conv_diff_bdim(f, uadv, sigma, u0, mu0, uout, G, d.nu, d.perdir_mask, d.scheme, dt.back(), pre, post, cl, s, G.k1 - 2, 1 << 30, want_q1);
     }
     WL_TRY(sync_u(s));
-    BcFold fr = fold_req(2);
+    BcFold fr{fold_ok(2) ? 1 : 0, {d.uBC[0], d.uBC[1], d.uBC[2]}};
     fr.proj_x = df.proj_pending;
     fr.dt_dev = dt_dev;
     WL_TRY(wl::conv_diff_bdim(f, uadv, sigma, u0, mu0, uout, G, d.nu, d.perdir_mask, d.scheme, dt.back(), pre, post, cl, s, -(1 << 30), 1 << 30, want_q1, &fr));
@@ -215,7 +215,7 @@ struct wl_sim {
   bool head_fused_ok() const { return head_fused_path() && !comm && (!resjac_force_redo || redo_unannounced); }
   bool bcdefer_ok(bool second) const {
     if (!(use_bcdefer && in_step && !df.bc_folded && fold_ok(1) && head_fused_ok())) return false;
-    return !second || (use_fuse_cfl && us && wl::project_cfl_pair_path(G, mg->lv[0].cl));
+    return !second || (use_fuse_cfl && us && wl::tail_caps_cfl(G, mg->lv[0].cl).usub);      // (the corrector's tail must put U on load: wl_project.hpp)
   }
   int bc_u_or_defer(bool second, hipStream_t s) {
     if (bcdefer_ok(second)) { df.bc_deferred = true; n_bcdefer++; return 0; }
@@ -298,8 +298,8 @@ struct wl_sim {
   bool use_pdefer = true;
   long n_pdefer = 0;             // tails that skipped the store
   float* p_home = nullptr;       // caller-owned p
-  // the projection tails with four cells per thread and 16-byte accesses (option "tailwide", k_project_wide in wl_poisson.hip): the same statements per cell, the
-  // same launches; taken where the launchers find that the shape and the arrays allow it (they report it: BcFold::wide_ran), everything else runs the one- and two-cell kernels
+  // the projection tails with four cells per thread and 16-byte accesses (option "tailwide", k_project_wide in wl_project.hip): the same statements per cell, the
+  // same launches; taken where the launchers find that the shape and the arrays allow it (they report it: TailRep::wide), everything else runs the one- and two-cell kernels
   bool use_tailwide = true;
   long n_tailwide = 0;           // tails that ran in that form
   // not fused_nobody_conv(): nothing between a tail and the next head goes through the spare velocity array, so `us` is not asked for
@@ -330,15 +330,19 @@ struct wl_sim {
   //   SplitInPlace   the same on the three plane ranges of a body
   //   Loader         left to the corrector's loader ("tailfuse"): at most p = x/Δt is launched here
   enum class Tail { PairCfl, InPlace, SplitInPlace, Loader };
-  struct TailPlan { Tail form; ZSplit z; bool gateable; };      // gateable: the form honours a device flag `go` (queued ahead of the solver's convergence read, "tailspec")
-  struct TailDone { int wide = 0; bool skips_p = false; };      // what the launch did: ran four cells per thread (the launcher's report, BcFold::wide_ran) / left p = x/Δt to the next fused head
+  // caps: what the launcher of the form can do on this level (wl_project.hpp; nothing for the split forms and the loader); gateable: the tail may be queued ahead
+  // of the solver's convergence read behind a device flag `go` ("tailspec")
+  struct TailPlan { Tail form; ZSplit z; wl::TailCaps caps; bool gateable; };
+  struct TailDone { wl::TailRep rep; bool skips_p = false; };      // what the launch did: the launcher's report (folded stores, four cells per thread) / left p = x/Δt to the next fused head
   bool pair_tail_cfl(bool with_cfl) const { return with_cfl && use_fuse_cfl && us && !d.exitBC && !d.perdir_mask; }
   TailPlan plan_tail(const ProjCall& c) const {
     TailPlan t; t.z = zsplit();
     t.form = pair_tail_cfl(c.with_cfl) ? Tail::PairCfl : t.z.on ? Tail::SplitInPlace : (c.corrector_follows && tailfuse_ok()) ? Tail::Loader : Tail::InPlace;
-    t.gateable = t.form == Tail::InPlace || (t.form == Tail::PairCfl && !t.z.on && wl::project_cfl_pair_path(G, mg->lv[0].cl) && (!df.bc_deferred || fold_req(1).on));
+    t.caps = t.form == Tail::InPlace ? wl::tail_caps_inplace(G, mg->lv[0].cl) : (t.form == Tail::PairCfl && !t.z.on) ? wl::tail_caps_cfl(G, mg->lv[0].cl) : wl::TailCaps{};
+    t.gateable = t.caps.gate && (t.form == Tail::InPlace || !df.bc_deferred || takes_deferred_bc(t));
     return t;
   }
+  bool takes_deferred_bc(const TailPlan& t) const { return fold_ok(1) && t.caps.usub; }      // the corrector's tail reads u as the deferred BC! would have left it; otherwise flush_bc comes first
   bool skip_p_now(const ProjCall& c) const {      // decided per launch: a back-off during the head withdraws it
     if (!pdefer_ok()) return false;
     if (c.with_cfl) return c.step_follows && !obs.reads_p_after_this_step();   // the corrector's tail: the next reader is the next step's head — unless an observer of this step reads p first
@@ -349,15 +353,14 @@ struct wl_sim {
   int launch_tail(const TailPlan& plan, const ProjCall& c, float dtl, const float* go, TailDone* done, hipStream_t s) {
     const wl_mg::Level& l0 = mg->lv[0];
     *done = TailDone{};
-    BcFold fr = fold_req(1); fr.go = go;
-    fr.wide = use_tailwide ? 1 : 0; fr.wide_ran = &done->wide;
+    wl::TailReq rq; rq.U = fold_ok(1) ? d.uBC : nullptr; rq.go = go; rq.wide = use_tailwide;
     switch (plan.form) {
       case Tail::PairCfl:
         if (plan.z.on) { WL_TRY(flush_bc(s)); WL_TRY(wl::project_cfl_split(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, l0.clp, plan.z.na, plan.z.nb, mg->ws, WL_RF_CFL, s, store_f ? 1 : 0)); break; }
-        if (df.bc_deferred && !(fr.on && wl::project_cfl_pair_path(G, l0.cl))) WL_TRY(flush_bc(s));
-        fr.usub = df.bc_deferred ? 1 : 0;      // flux_out reads the wall-normal boundary faces of the corrector's output: U on load
-        done->skips_p = wl::project_cfl_pair_path(G, l0.cl) && skip_p_now(c);
-        WL_TRY(wl::project_cfl(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, mg->ws, WL_RF_CFL, s, store_f ? 1 : 0, &fr, done->skips_p)); df.bc_folded = fr.on != 0;
+        if (df.bc_deferred && !takes_deferred_bc(plan)) WL_TRY(flush_bc(s));
+        rq.usub = df.bc_deferred;      // flux_out reads the wall-normal boundary faces of the corrector's output: U on load
+        rq.skip_p = done->skips_p = plan.caps.skip_p && skip_p_now(c);
+        WL_TRY(wl::project_cfl(us, u, mu0, p, ps, sigma, G, dtl, l0.cl, mg->ws, WL_RF_CFL, s, store_f ? 1 : 0, rq, &done->rep)); df.bc_folded = done->rep.folded;
         break;
       case Tail::SplitInPlace: WL_TRY(wl::project_unscale_split(u, mu0, p, ps, G, dtl, l0.cl, l0.clp, plan.z.na, plan.z.nb, s)); break;
       case Tail::Loader:        // (with the store skipped this tail launches nothing at all: the corrector's head takes x with the pending divisor)
@@ -365,8 +368,8 @@ struct wl_sim {
         if (!done->skips_p) WL_TRY(wl::div_scalar_to(ps, p, dtl, (size_t)G.cs, s));
         break;
       case Tail::InPlace:
-        done->skips_p = skip_p_now(c);
-        WL_TRY(wl::project_unscale(u, mu0, p, ps, G, dtl, l0.cl, s, &fr, done->skips_p)); df.bc_folded = fr.on != 0;
+        rq.skip_p = done->skips_p = plan.caps.skip_p && skip_p_now(c);
+        WL_TRY(wl::project_unscale(u, mu0, p, ps, G, dtl, l0.cl, s, rq, &done->rep)); df.bc_folded = done->rep.folded;
         break;
     }
     return 0;
@@ -439,7 +442,7 @@ struct wl_sim {
       WL_TRY(wl::combine_results(comm, mg->ws, s));   // max over ranks — issued BEFORE the u exchange starts on the other stream, so that
       std::swap(u, us); df.cfl_done = true;           // exchange stays in flight across the Δt read-back and the next predictor's interior
     }
-    if (done.wide) n_tailwide++;
+    if (done.rep.wide) n_tailwide++;
     if (done.skips_p) { df.p_scale_pending = dtl; n_pdefer++; }      // p stays the solver's x; no store, no swap
     else swap_p();
     return plan.form == Tail::Loader ? 0 : bc_u(s);
