@@ -170,7 +170,11 @@ int wl_mg_level_grid(const wl_mg* mg, int level, wl_grid* out);
 /* name ∈ "L","D","iD","x","eps","r","z" — device pointer of that level's array (tests read pois.levels[k].D etc.).
  * On the multigrid handle of a simulation composite, whose option "rskip" is on by default, the smoother does not store residuals nobody reads: level 0's "r" is brought up to date by this call
  * (if the last smooth! skipped its store: one launch on the stream that smooth! ran on, waited for; ask again after every solve), a coarse level's "r" is
- * unspecified scratch. */
+ * unspecified scratch.
+ * Writing through these pointers: between public calls the interior cells of every level's "r" and "eps" and of a coarse level's "z", and EVERY cell of a coarse
+ * level's "x", are dead — the library writes them before it reads them, whatever they hold (Vcycle!'s fill!(coarse.x,0) clears the ghost cells too, also where it
+ * is folded into the level's Jacobi!).  The ghost cells of "r", "eps" and "z" are not: the kernels read them as the zeros they have held since wl_mg_create
+ * (a ghost ϵ is multiplied by L = 0, which stops a finite value and not a NaN) — a writer leaves them zero.  tests/test_gpu_deadstore.py overwrites the dead cells. */
 float* wl_mg_level_field(const wl_mg* mg, int level, const char* name);
 int wl_mg_vcycle(wl_mg* mg, int level, float omega, void* stream);
 int wl_mg_smooth(wl_mg* mg, int level, int it, float omega, void* stream);      /* smooth! = GaussSeidelRB! on one level (:106) */
@@ -212,7 +216,10 @@ typedef struct wl_sim_desc {
                   (the Julia binding re-points its HipArray objects; the three buffers stay the caller's to free);
        us NULL  : pointers never move — `u⁰ .= u` is a copy and conv_diff!/BDIM! run as separate passes (slower).
      Convective exit (exitBC=1, single domain): the buffers rotate as well; BC! leaves the x-exit face of u alone (saveexit, src/core.jl:207),
-     so that face is copied from the old role holder to the new one at each rotation (one strided plane).  On z-slabs exitBC flows keep the copy. */
+     so that face is copied from the old role holder to the new one at each rotation (one strided plane).  On z-slabs exitBC flows keep the copy.
+     What the scratch arrays hold at wl_sim_create, and between calls, does not matter: every cell of `us` (whichever buffer is in that role) and of `f`, and
+     the interior cells of `sigma`, are written before they are read — uninitialised memory will do (the Julia binding passes `similar(u)`); σ's GHOST cells are
+     live: conv_diff! leaves stale fluxes in the upper ones, nothing ever writes the lower ones, and CFL's maximum(σ) sees them all, as in the reference. */
   float *us;
 } wl_sim_desc;
 int wl_sim_create(wl_sim** out, const wl_sim_desc* desc);

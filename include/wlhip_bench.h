@@ -66,6 +66,27 @@ int wl_meshsdf_last_bricks(uint64_t* searched, uint64_t* skipped);
  * default) nothing is fenced; ms4[0], which needs no fence, is recorded either way.  For tools/meshvel_bench.py. */
 int wl_meshsdf_time(int on);
 int wl_meshsdf_last_times(double* ms4);
+/* ---- test hook (tests/deadstore.py): the scratch no entry point hands out.  wl_sim_scratch_fill first settles whatever is pending, as wl_sim_field does (and the
+ * finest level's residual where option "rskip" left it unstored), then writes the 32-bit word `bits` on `stream` into everything the handle and its wl_mg own
+ * that is DEAD between public calls — written by the library before it is read again, whatever it holds:
+ *   1. the pressure array of the pair {p, spare} that does not hold the pressure: every cell, ghost cells included — cells(level 0) words
+ *      (what the handle knows of the ghost shells of the pair is forgotten: the next fused head checks them again);
+ *   2. every level's ϵ_mid and r′ of the blocked smoother (wl_mg::Level::em, rs): interior cells — 2·interior(level) words per level;
+ *   3. every exchange buffer W (csrc/wl_abwide.hpp; 3-D levels that have one): on the interior planes the interior rows, whole 512-byte segments, padding slots
+ *      included — (nz − 2)·(ny − 2)·⌈(nx − 1)/60⌉·128 words per such level;
+ *   4. the per-block partials of the reduction workspace: 65536 × (two doubles + one float) = 327680 words;
+ *   5. the partial sums of the force bands that exist (the recorder's, the immediate read-out's): 24 words per tile of their capacity — none before
+ *      wl_sim_set_force_record / wl_sim_forces_bodyset.
+ * It leaves alone what must keep a value: the ghost cells of em and rs and W's ghost rows and planes (zero since allocation, read by kernel B), the 16 result
+ * slots of the reduction workspace, the body masks, the band lists, probe, force and tracer records and positions, the mean-flow sums.  Caller-visible arrays
+ * (f, σ, us, the levels' r, ϵ, x, z) are the caller's to overwrite through wl_sim_field / wl_mg_level_field.
+ * Returns the number of 4-byte words written, −1 on error (z-slab handles: single domain only).  wl_sim_scratch_keep is the same call — the same settling, the
+ * same launches, the same return value — with every word left as it is: for the twin that a filled handle is compared with.  wl_sim_scratch_fill_regions
+ * writes only the regions whose bit is set (bit i − 1: region i of the list) and counts those: for finding which region a difference comes from.  None of them
+ * is on the step path. */
+int wl_sim_scratch_fill(wl_sim* s, uint32_t bits, void* stream);
+int wl_sim_scratch_fill_regions(wl_sim* s, uint32_t bits, uint32_t regions, void* stream);
+int wl_sim_scratch_keep(wl_sim* s, void* stream);
 
 #ifdef __cplusplus
 }

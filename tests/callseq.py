@@ -405,12 +405,20 @@ class CallerDev:
     def mom_steps_(self, k):
         self.sim.check(self.sim.lib.wl_sim_mom_steps(self.sim.h, int(k), self._stream())); self._after()
 
+    def phase_(self, k):
+        self.sim.check(self.sim.lib.wl_sim_phase(self.sim.h, int(k), self._stream())); self._after()
+
     def field(self, name):
         self._after()
         return self.sim.field(name)
 
     def set_sgs(self, on):
         self.sim.check(self.sim.lib.wl_sim_set_sgs(self.sim.h, 1 if on else 0, 0.17 if on else 0.0, 1.0)); self._after()
+
+    def set_forcing(self, acc):
+        import ctypes as C
+        a = None if acc is None else (C.c_float * 3)(*([float(v) for v in acc] + [0.0] * (3 - len(acc))))
+        self.sim.check(self.sim.lib.wl_sim_set_forcing(self.sim.h, None, a, a)); self._after()
 
     def set_dt_last(self, v):
         self.sim.check(self.sim.lib.wl_sim_set_dt_last(self.sim.h, float(v))); self._after()
@@ -449,17 +457,16 @@ class CallerDev:
         self.sim.close()
 
 
-def make(family, w):
-    """(A, B): the default handle with the size gates opened, the eager handle"""
+def make_one(family, w, eager, caller_eager=False, **caller_kw):
+    """one handle of the family: the default one with the size gates opened, or the eager one.  The eager handle of the caller family is handle-owned, as make()
+    pairs it; caller_eager: caller-owned with the deferrals off (tests/deadstore.py compares two handles of one kind).  caller_kw: further arguments of CallerOwnedSim"""
     if family in BODY_CASE:
         import bodypaths_ref as bp
         from test_gpu_bodypaths import handle
         case = next(c for c in bp.CASES if c["id"] == BODY_CASE[family])
-        A = Dev(w, handle(w, case, dict(GATES, zsplit=2)), 1, case)
-        B = Dev(w, handle(w, case, dict(GATES, **EAGER, **EAGER_BODY)), 0, case)
-        for h in (A, B):
-            h.measure_(0)
-        return A, B
+        h = Dev(w, handle(w, case, dict(GATES, **EAGER, **EAGER_BODY)), 0, case) if eager else Dev(w, handle(w, case, dict(GATES, zsplit=2)), 1, case)
+        h.measure_(0)
+        return h
     dims = DIMS[family]
     if family in ("box", "caller"):
         u_init = np.asfortranarray(np.random.default_rng(137).uniform(-0.4, 0.4, size=tuple(n + 2 for n in dims) + (3,)).astype(f32))
@@ -468,17 +475,22 @@ def make(family, w):
         new = lambda: w.FusedSimulation(dims, (0.0,) * 3, dims[0], U=1, nu=dims[0] / 1600.0, ic="tgv")
     else:
         new = lambda: w.FusedSimulation(dims, (0.0,) * 3, dims[0], U=1, nu=dims[0] / 1600.0, ic="tgv_periodic", perdir=(1, 3))
-    B = Dev(w, new())
-    for k, v in dict(GATES, **EAGER).items():
-        set_opt(B, k, v)
-    if family == "caller":
+    if family == "caller" and (caller_eager or not eager):
         from test_gpu_callerowned import CallerOwnedSim
-        A = CallerDev(w, CallerOwnedSim(w, dims, UBC, 0.02, u_init, True))
+        h = CallerDev(w, CallerOwnedSim(w, dims, UBC, 0.02, u_init, caller_kw.pop("with_spare", True), **caller_kw))
     else:
-        A = Dev(w, new())
-    for k, v in GATES.items():
-        set_opt(A, k, v)
-    return A, B
+        h = Dev(w, new())
+    for k, v in (dict(GATES, **EAGER) if eager else GATES).items():
+        set_opt(h, k, v)
+    return h
+
+
+def make(family, w):
+    """(A, B): the default handle with the size gates opened, the eager handle"""
+    if family in BODY_CASE:
+        return make_one(family, w, False), make_one(family, w, True)
+    B = make_one(family, w, True)
+    return make_one(family, w, False), B
 
 
 def replay(family, seed, upto=None, w=None):

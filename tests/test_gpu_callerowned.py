@@ -21,7 +21,9 @@ class CallerOwnedSim:
     """What the Julia side does, in Python: allocate the Flow fields as device arrays (Flow ctor, src/Flow.jl:133-147), create the
     composite on them, step, follow the array roles."""
 
-    def __init__(self, w, dims, uBC, nu, u_init, with_spare, body=None, exitBC=False):
+    def __init__(self, w, dims, uBC, nu, u_init, with_spare, body=None, exitBC=False, fill=None):
+        """fill: None — the scratch arrays are zeros; a pattern of tests/deadstore.py ("nan", "garbage") — f, the spare and σ's interior hold it instead, as
+        `similar(a.u)` hands the library uninitialised memory (tests/test_gpu_deadstore.py)"""
         from waterlily_jl_amd._lib import check, lib, wl_sim_desc
         self.w, self.check, self.lib = w, check, lib()
         D = len(dims)
@@ -36,6 +38,12 @@ class CallerOwnedSim:
         w.BC_(self.arr["mu0"], (0,) * D)                                    # BC!(μ₀,0)                     :145
         if with_spare:
             self.arr["us"] = w.jl_zeros(Ng + (D,))
+        if fill is not None:
+            import deadstore
+            for k in ("f", "us", "sigma"):
+                if k in self.arr:
+                    v = deadstore.values(fill, tuple(self.arr[k].shape), (k, "create"))
+                    self.arr[k] = w.to_device(v if k != "sigma" else deadstore.interior_of(v, np.zeros_like(v)))
         self.role = {k: k for k in ("u", "u0", "us") if k in self.arr}      # role -> buffer name
         if body is not None:                                                # measure!(flow,body)           src/WaterLily.jl:104
             import waterlily_jl_amd.simulation as S

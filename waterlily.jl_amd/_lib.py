@@ -185,6 +185,9 @@ SIGNATURES = {
     "wl_reset_process_options": (i32, []),
     "wl_placement_scores": (i32, [C.POINTER(C.c_double), i32]),
     "wl_sim_counter": (i32, [P, C.c_char_p, C.POINTER(C.c_long)]),
+    "wl_sim_scratch_fill": (i32, [P, C.c_uint32, P]),
+    "wl_sim_scratch_fill_regions": (i32, [P, C.c_uint32, C.c_uint32, P]),
+    "wl_sim_scratch_keep": (i32, [P, P]),
     "wl_prof_enable": (i32, [i32]),
     "wl_prof_read": (i32, [i32, C.POINTER(i32), C.POINTER(f64)]),
     "wl_sim_pressure_force_sphere": (i32, [P, C.POINTER(f32), f32, C.POINTER(f64), P]),

@@ -337,7 +337,10 @@ __global__ void k_bdim_u_m(GridX g, float* __restrict__ uout, const float* __res
   for (int a = 0; a < D; a++) {
     const long oa = (long)a * g.cs + o;
     float s = 0.f;
-    for (int b = 0; b < D; b++) s += mu1[(long)(a + b * D) * g.cs + o] * (f[oa + st[b]] - f[oa - st[b]]);     // μddn :20-26
+    // μddn :20-26.  f is read only where its coefficient is not zero: conv_diff_bdim_body keeps f outside the near workgroups only for the neighbours of cells
+    // with a non-zero μ₁ (needf) — next to any other cell of a near workgroup f is whatever the array held, and 0·f is not 0 for every f (same bits otherwise: a
+    // skipped term is ±0 added to a sum that starts at +0)
+    for (int b = 0; b < D; b++) { const float c1 = mu1[(long)(a + b * D) * g.cs + o]; if (c1 != 0.f) s += c1 * (f[oa + st[b]] - f[oa - st[b]]); }
     const float x = (s / 2 + V[oa]) + mu0[oa] * f[oa];
     float un = (pre == 0.f) ? x : (uin[oa] * pre + x);
     if (scale_after) un = un * post;

@@ -366,8 +366,8 @@ int wl_mg::restrict_to_coarse(int l, bool to_tail, hipStream_t s) {
     WL_TRY(wl::restrict_(coarse.r, coarse.view, fine.r, fine.x_, s));
     WL_TRY(wl::allgather_planes(comm, coarse.r, coarse.view, 1, s));
   } else WL_TRY(wl::restrict_(coarse.r, coarse.x_, fine.r, fine.x_, s));
-  // the fill! is folded into the coarse level's Jacobi! when that is what touches x next (single-domain level, one-pass Jacobi kernels): its ghost cells
-  // are zero since allocation and nothing writes them
+  // the fill! is folded into the coarse level's Jacobi! when that is what touches x next (single-domain level, one-pass Jacobi kernels): that launch writes
+  // x = ω·ϵ on the interior and clears x's ghost cells (wl_xzero_ghosts) — every cell, as fill! does, whatever the array held
   coarse.xzero = skip_fill && !to_tail && l + 2 < (int)lv.size() && !perdir && !coarse.dist && !coarse.has_view;
   return coarse.xzero ? 0 : wl::fill(coarse.x, 0.f, (size_t)coarse.x_.cs, s);
 }

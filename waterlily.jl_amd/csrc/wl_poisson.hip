@@ -320,6 +320,17 @@ __global__ void k_gs_init_sweep1(GridX g, float* __restrict__ eps, const float* 
   if (D == 3) s -= (E(o - g.sz) * L[2 * g.cs + o] + E(o + g.sz) * L[2 * g.cs + o + g.sz]);
   eps[o] = s * iD[o];
 }
+// fill!(coarse.x,0) folded into Jacobi! (xzero): fill! clears EVERY cell, so the launch also clears the cells it does not compute — x's ghost cells, which the
+// prolongation and the smoothers read.  The thread of an in-plane ghost cell clears it on its own plane; the threads of the first and the last interior plane
+// clear the ghost planes beyond them (3-D).  Whole single-domain levels only (wl_mg::restrict_to_coarse): interior planes 1 … nz−2, whatever sub-range g.k0, g.k1 name
+template <int D>
+__device__ __forceinline__ void wl_xzero_ghosts(const GridX& g, float* __restrict__ x, long m, int k, bool ghost_ij) {
+  if (ghost_ij) x[m + (long)k * g.sz] = 0.f;
+  if (D == 3) {
+    if (k == 1) x[m] = 0.f;
+    if (k == g.nz - 2) x[m + (long)(g.nz - 1) * g.sz] = 0.f;
+  }
+}
 // Jacobi!(it=1,ω): ϵ=r·iD ; r -= ωAϵ ; x += ωϵ in ONE pass.  The new residual goes to `rout` (≠ r: neighbours still read
 // the old r); the caller then swaps its r/ϵ buffers.  36 instead of 12+36 B/cell.                 src/Poisson.jl:111-114
 // constant-coefficient Jacobi!: L, D, iD evaluated from the cell position (wl::ConstL) — 16 instead of 32 B/cell
@@ -330,8 +341,11 @@ __global__ void k_jacobi_pp_cl(GridX g, float* __restrict__ rout, const float* _
   __syncthreads();
   int i, j; long m; int pz;
   wl_tile(g, m, pz);
-  if (!cell_ij(g, m, i, j) || !interior_ij(g, i, j)) return;
+  if (!cell_ij(g, m, i, j)) return;
   const int k = g.k0 + pz;
+  const bool in = interior_ij(g, i, j);
+  if (xzero) wl_xzero_ghosts<D>(g, x, m, k, !in);
+  if (!in) return;
   const long o = m + (long)k * g.sz;
   const int I0 = i + 1, I1 = j + 1, I2 = (D == 3) ? g.gk + k + 1 : 3;
   const int N2 = (D == 3) ? g.gnz : 8;
@@ -369,7 +383,9 @@ __global__ void k_jacobi_march_cl(GridX g, float* __restrict__ rout, const float
   if (SHIFT) c = wl_shift_due(*sum, n_inside) ? wl_shift_mean(*sum, n_inside) : 0.f;
   float acc = 0.f, mx = 0.f;      // a thread's |r| over its ≤ zchunk planes in Float32, across threads in Float64
   const int ks = g.k0 + pz * zchunk, ke = (ks + zchunk < g.k1) ? ks + zchunk : g.k1;
-  const bool live = cell_ij(g, m, i, j) && interior_ij(g, i, j) && ks < ke;
+  const bool cell = cell_ij(g, m, i, j);
+  const bool live = cell && interior_ij(g, i, j) && ks < ke;
+  if (xzero && cell && !live) for (int k = ks; k < ke; k++) wl_xzero_ghosts<3>(g, x, m, k, true);      // a ghost column of x (live columns: in the march below)
   if (!SHIFT && !live) return;
   if (live) {
   const int I0 = i + 1, I1 = j + 1;
@@ -400,6 +416,7 @@ __global__ void k_jacobi_march_cl(GridX g, float* __restrict__ rout, const float
     s += ((rm * pick(id0, czm)) * lz + (rp * pick(id0, czp)) * lzp);
     rout[o] = r0 - w * s;
     x[o] = (xzero ? 0.f : x[o]) + w * e0;          // xzero: x ≡ 0 on entry (fill!(coarse.x,0) of the V-cycle folded in)
+    if (xzero) wl_xzero_ghosts<3>(g, x, m, k, false);
     rm = r0; r0 = rp;
   }
   }
@@ -413,8 +430,11 @@ __global__ void k_jacobi_pp(GridX g, float* __restrict__ rout, const float* __re
                             const float* __restrict__ Dg, const float* __restrict__ iD, float w, int xzero) {
   int i, j; long m; int pz;
   wl_tile(g, m, pz);
-  if (!cell_ij(g, m, i, j) || !interior_ij(g, i, j)) return;
+  if (!cell_ij(g, m, i, j)) return;
   const int k = g.k0 + pz;
+  const bool in = interior_ij(g, i, j);
+  if (xzero) wl_xzero_ghosts<D>(g, x, m, k, !in);
+  if (!in) return;
   const long o = m + (long)k * g.sz;
   // ghost cells of r, iD and ϵ are zero in the arrays a wl_mg handle owns, so r·iD of a ghost reproduces its stored ϵ (=0)
   auto E = [&](long oo) -> float { return r[oo] * iD[oo]; };

@@ -8,6 +8,7 @@
 #include "wl_common.hpp"
 #include <algorithm>
 #include "wl_mg.hpp"
+#include "wl_abwide.hpp"
 #include "wl_body.hpp"
 #include "wl_pdefer.hpp"
 #include "wl_project.hpp"
@@ -48,6 +49,18 @@ __global__ void k_apply_const(GridX g, float* __restrict__ u, float U0, float U1
 
 // Δt = min(10, 1/(max σ + 5ν))  (src/Flow.jl:166, CFL :234-237) on the device: the statement wl_sim::cfl evaluates on the host from the same maximum
 __global__ void k_dt_from_cfl(float* __restrict__ res_f, int in_slot, int out_slot, float nu) { res_f[out_slot] = fminf(10.f, 1.0f / (res_f[in_slot] + 5 * nu)); }
+// wl_sim_scratch_fill: `bits` into the interior cells of a dense single-domain array — ghost cells keep what they hold.  One thread per interior cell, by a flat
+// index over the interior box; keep: every cell gets back the word it held (the same launch, nothing changes)
+__global__ void k_fill_interior_bits(uint32_t* __restrict__ a, int nx, int ny, long sz, int k0, int k1, long n, uint32_t bits, int keep) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int wx = nx - 2, wy = ny - 2;
+  const long q = t / wx;
+  const int i = 1 + (int)(t - q * wx), j = 1 + (int)(q % wy), k = k0 + (int)(q / wy);
+  if (k >= k1) return;
+  const long o = i + (long)j * nx + (long)k * sz;
+  a[o] = keep ? a[o] : bits;
+}
 }  // namespace
 
 #define DSEL(D, KERN, ...)                                                           \
@@ -693,6 +706,45 @@ float* wl_sim_field(wl_sim* s, const char* name) {
   return nullptr;
 }
 wl_mg* wl_sim_pois(wl_sim* s) { return s->mg; }
+// ---- wl_sim_scratch_fill / wl_sim_scratch_keep (wlhip_bench.h): a word into everything the handle and its wl_mg own that no public call reaches and that is dead
+// between public calls.  Not on the step path.  write = false: the same settling and the same launches, every word stays
+static long scratch_fill(wl_sim* s, uint32_t bits, uint32_t regions, bool write, hipStream_t q) {
+  if (!s || s->comm) { wl_set_error("wl_sim_scratch_fill: single-domain handles only"); return -1; }
+  if (s->settle(q) != 0 || s->mg->settle_r(q) != 0) return -1;      // nothing pending: p is the pressure, the finest r is stored (the r-only launch reads em, rs, W)
+  long words = 0;
+  auto whole = [&](void* a, size_t n) -> int {
+    words += (long)n;
+    if (write && n) WL_HIP(hipMemsetD32Async((hipDeviceptr_t)a, (int)bits, n, q));
+    return 0;
+  };
+  auto interior = [&](float* a, const GridX& g) -> int {
+    const int k0 = g.D == 3 ? 1 : 0, k1 = g.D == 3 ? g.nz - 1 : 1;
+    const long n = (long)(g.nx - 2) * (g.ny - 2) * (k1 - k0);
+    if (!a || n <= 0) return 0;
+    words += n;
+    hipLaunchKernelGGL(k_fill_interior_bits, dim3((unsigned)((n + WL_BLOCK - 1) / WL_BLOCK)), dim3(WL_BLOCK), 0, q, (uint32_t*)a, g.nx, g.ny, g.sz, k0, k1, n, bits, write ? 0 : 1);
+    WL_LAUNCH_CHECK(); return 0;
+  };
+  // the pressure pair: p lives in one array, the other one is rewritten by the next head or tail — its ghost cells too, so what is known of the shell is forgotten
+  if (regions & 1u) { if (whole(s->ps, (size_t)s->G.cs) != 0) return -1; if (s->p_shell != 2) s->p_shell = -1; }
+  for (wl_mg::Level& v : s->mg->lv) {
+    if ((regions & 2u) && (interior(v.em, v.x_) != 0 || interior(v.rs, v.x_) != 0)) return -1;      // ϵ_mid and r′ of the blocked smoother (their ghost cells stay zero: kernel B reads them)
+    if ((regions & 4u) && v.wx && v.g.D == 3) {      // W: the interior rows of an interior plane are contiguous — whole segments, the padding slots included
+      const size_t row = wl::abw_pitch(v.g.nx) / sizeof(float), n = (size_t)(v.g.ny - 2) * row;
+      for (int k = 1; k < v.g.nz - 1; k++) if (whole(v.wx + ((size_t)k * v.g.ny + 1) * row, n) != 0) return -1;
+    }
+  }
+  // the per-block partials of the reduction workspace (two double arrays and one float array of WL_MAXPART entries): every reduction writes the partials it reads;
+  // the 16 result slots behind them keep their values
+  if ((regions & 8u) && whole(s->mg->ws.pa, (size_t)WL_MAXPART * 5) != 0) return -1;
+  // the observers' staging: the partial sums of the force bands (12 doubles per tile of their capacity, written by every run before its finish reads them)
+  if (regions & 16u) for (wl::ForceBand* b : {&s->obs.fband, &s->obs.fimm}) if (b->part && whole(b->part, (size_t)b->part_cap * 24) != 0) return -1;
+  if (words > 0x7fffffffL) { wl_set_error("wl_sim_scratch_fill: more than 2^31 words"); return -1; }
+  return words;
+}
+int wl_sim_scratch_fill(wl_sim* s, uint32_t bits, void* st) { return (int)scratch_fill(s, bits, ~0u, true, wl_stream(st)); }
+int wl_sim_scratch_fill_regions(wl_sim* s, uint32_t bits, uint32_t regions, void* st) { return (int)scratch_fill(s, bits, regions, true, wl_stream(st)); }
+int wl_sim_scratch_keep(wl_sim* s, void* st) { return (int)scratch_fill(s, 0u, ~0u, false, wl_stream(st)); }
 int wl_sim_grid(const wl_sim* s, wl_grid* out) { *out = s->g; return 0; }
 int wl_sim_init_flow(wl_sim* s, void* st) {                                               // Flow ctor :141-142
   hipStream_t q = wl_stream(st);

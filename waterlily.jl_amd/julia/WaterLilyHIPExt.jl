@@ -307,7 +307,7 @@ function composite!(a::HFlow{D}, b::HipMultiLevel) where {D}
     @assert b.x === a.p && b.L === a.μ₀ && b.z === a.σ "the composite time step needs the MultiLevelPoisson built on this flow's p, μ₀, σ"
     uBC = a.uBC isa Tuple ? pad3(a.uBC) : pad3(ntuple(i -> Float32(a.uBC(i, ntuple(_ -> 0f0, D), 0f0)), D))     # (a Function here is uniform in x: mom_step! checked)
     N = size(a.p) .- 2
-    spare = (b.spare === nothing || size(b.spare) != size(a.u)) ? similar(a.u) : b.spare
+    spare = (b.spare === nothing || size(b.spare) != size(a.u)) ? similar(a.u) : b.spare      # (uninitialised on purpose: the library writes every cell of the spare before it reads it — wlhip.h, tests/test_gpu_deadstore.py)
     d = Ref(WlSimDesc(D, ntuple(i -> i <= D ? Int32(N[i]) : Int32(1), 3), uBC, a.ν, a.Δt[end], pmask(a.perdir), Int32(a.exitBC), scheme(a.λ), Int32(has_body(a)),
                       a.u.ptr, a.u⁰.ptr, a.f.ptr, a.p.ptr, a.σ.ptr, a.V.ptr, a.μ₀.ptr, a.μ₁.ptr, spare.ptr))   # (exitBC flows too: `u⁰ .= u` stays a pointer rotation; the fused CFL tail is skipped by the library itself)
     h = Ref{Ptr{Cvoid}}()
