@@ -606,6 +606,41 @@ int wl_sim_meanflow_uu(wl_sim* s, float* out, int tau, void* hip_stream);
 /* meanflow.t: copies min(length, cap) entries to host `out` (NULL: none) and returns the length */
 int wl_sim_meanflow_t(const wl_sim* s, float* out, int cap);
 
+/* ---- separable terms: position-dependent boundary profiles and body forces (csrc/wl_terms.hip) ---------------------------
+ * A closure uBC(i,x,t) or g(i,x,t) cannot cross this boundary; its separable form can:
+ *     uBC(i,x,t) = Σₖ bₖ(t)·Fₖ[I,i]        g(i,x,t) = Σₖ gₖ(t)·Fₖ[I,i]        k < K ≤ 4
+ * with Fₖ device arrays of the shape of u (cs·D floats) that hold the spatial factor at loc(i,I), and K host coefficients per evaluation.  A steady
+ * profile is K = 1, b = 1; the rotating frame of test/test_flow.jl:142-158 is K = 4 with sin/cos coefficients.  accelerate! adds g + ∂ₜuBC on all cells
+ * (src/Flow.jl:69-73): the acceleration coefficient of term k is aₖ(t) = gₖ(t) + bₖ′(t), on the same field.
+ * The combination is formed in one order, every product and sum rounded to Float32, no term skipped (a zero coefficient is multiplied and added):
+ *     s = c₀·F₀[q] ;  s = s + cₖ·Fₖ[q]  for k = 1 … K−1.
+ *
+ * Leaves on caller arrays (F: K host pointers to device arrays, host_c / host_b: K host floats; asynchronous on hip_stream):
+ *   wl_accel_terms    r[q] = r[q] + s over the cs·D elements of r — accelerate!(r,t,g,uBC).  One launch, (K+2)·4 B per element; 16-byte accesses when cs·D
+ *                     is a multiple of 4 and r and every Fₖ are 16-byte aligned, one element per thread otherwise (the same statements).
+ *   wl_bc_vec_terms   BC!(a,uBC::Function,saveexit,perdir,t) (src/core.jl:201-219): what wl_bc_vec_fn does with Ub = the combination, formed on the fly — only
+ *                     the two outermost layers of the non-periodic directions of the Fₖ are read.
+ *   WL_EINVAL before any launch for: K outside 1 … 4, a NULL array, an Fₖ that is the output array, a non-finite coefficient.
+ *
+ * On a handle:
+ *   wl_sim_set_terms        the handle allocates K device arrays of cs·D floats, copies host_F[k] into them on hip_stream and synchronises it; it owns them.
+ *                           Coefficients in force are dropped.  K = 0 frees the arrays and restores the step of a handle that never had any, exactly.
+ *   wl_sim_term             the device pointer of term k, for callers that fill a term on the device (NULL: no such term).
+ *   wl_sim_set_term_coeffs  K floats each: acc0 = aₖ(t₀) (predictor), acc1 = aₖ(t₁) (corrector), bc1 = bₖ(t₁) (every BC!(u) of the step).  NULL acc0 and acc1:
+ *                           no acceleration from the terms (one of the two NULL: zeros); NULL bc1: the boundary values stay the tuple uBC.  They stay in
+ *                           force until the next call, so constant coefficients survive wl_sim_mom_steps.
+ * With acceleration coefficients the predictor and the corrector take the staged sequence conv_diff! -> sgs! -> accelerate! -> BDIM! -> scale_u! -> BC!
+ * (as for wl_sim_set_forcing, whose uniform launch comes first if it is on too); with boundary coefficients every BC!(u) of the step and of wl_sim_init_flow
+ * is the terms kernel (exitBC! is untouched) and nothing folds or defers BC!.  2-D and 3-D, with or without a body or the SGS model.
+ * Counters (wl_sim_counter): "term_accel" and "term_bc", launches of the two kernels by this handle so far.
+ * WL_EINVAL with the reason, before any launch or allocation, for: a z-slab handle; K outside 0 … 4; a NULL field; a non-finite value in a field; a
+ * non-finite coefficient; coefficients given while K = 0.  The stream-contract scenarios are tests/test_gpu_streams_terms.py. */
+int wl_accel_terms(float* r, int K, const float* const* F, const float* host_c, const wl_grid* g, void* hip_stream);
+int wl_bc_vec_terms(float* a, int K, const float* const* F, const float* host_b, const wl_grid* g, int saveexit, unsigned perdir_mask, void* hip_stream);
+int wl_sim_set_terms(wl_sim* s, int K, const float* const* host_F, void* hip_stream);
+float* wl_sim_term(wl_sim* s, int k);
+int wl_sim_set_term_coeffs(wl_sim* s, const float* acc0, const float* acc1, const float* bc1);
+
 /* ---- multi-GPU: z-slab decomposition, one process per GPU (NEW — the reference has no multi-device path,
  * /root/reference/README.md:153-155).  A wl_comm carries the two primitives the slab path needs, stream-ordered:
  * a nearest-neighbour plane exchange along z and an all-gather; scalars (Σr, L₁, L∞, max σ) are combined on

@@ -244,6 +244,11 @@ SIGNATURES = {
     "wl_sim_meanflow": (P, [P, i32, C.POINTER(sz)]),
     "wl_sim_meanflow_uu": (i32, [P, P, i32, P]),
     "wl_sim_meanflow_t": (i32, [P, C.POINTER(f32), i32]),
+    "wl_accel_terms": (i32, [P, i32, C.POINTER(P), C.POINTER(f32), G, P]),
+    "wl_bc_vec_terms": (i32, [P, i32, C.POINTER(P), C.POINTER(f32), G, i32, u32, P]),
+    "wl_sim_set_terms": (i32, [P, i32, C.POINTER(P), P]),
+    "wl_sim_term": (P, [P, i32]),
+    "wl_sim_set_term_coeffs": (i32, [P, C.POINTER(f32), C.POINTER(f32), C.POINTER(f32)]),
 }
 
 _lib = None

@@ -143,6 +143,44 @@ def accelerate_(r, t, g=None, uBC=None, duBC_dt=None):
     check(lib().wl_stream_sync(stream()))
 
 
+def tabulate(fn, dims):
+    """the spatial factor of a separable term: F[I,i] = fn(i, x) with x = loc(i,I) in Float32, evaluated ONCE per component, vectorised — fn(i, x)
+    receives i = 1..D and x as D broadcastable Float32 arrays (x[0] varies along the first axis, …) and returns an array (or a scalar) that broadcasts
+    to the ghosted shape.  dims: interior sizes.  Returns a Fortran-ordered (Ng…, D) Float32 array for FusedSimulation(terms=[…])."""
+    D = len(dims)
+    Ng = tuple(int(n) + 2 for n in dims)
+    F = np.empty(Ng + (D,), dtype=np.float32, order="F")
+    for i in range(1, D + 1):
+        x = []
+        for d in range(D):
+            sh = [1] * D
+            sh[d] = Ng[d]
+            # loc(i,I) = I − 1.5 − δ(i)/2 with the 1-based I = k + 1   src/core.jl:177
+            x.append((np.arange(1, Ng[d] + 1, dtype=np.float32) - np.float32(1.5) - np.float32(1 if d == i - 1 else 0) / np.float32(2)).reshape(sh))
+        F[..., i - 1] = np.broadcast_to(np.asarray(fn(i, x), dtype=np.float32), Ng)
+    return F
+
+
+def _term_args(F, c):
+    K = len(F)
+    assert K == len(c)
+    return K, (C.c_void_p * max(K, 1))(*[ptr(f) for f in F]), (C.c_float * max(K, 1))(*[float(v) for v in c])
+
+
+def accel_terms_(r, F, c):
+    """accelerate!(r,t,g,uBC) from separable terms on the device: r[I,i] += Σₖ c[k]·F[k][I,i] (one launch, wl_accel_terms)"""
+    K, Fp, cp = _term_args(F, c)
+    g = vgrid(r)
+    check(lib().wl_accel_terms(ptr(r), K, Fp, cp, C.byref(g), stream()))
+
+
+def BC_terms_(a, F, b, saveexit=False, perdir=()):
+    """BC!(a,uBC::Function,saveexit,perdir,t) with uBC = Σₖ b[k]·F[k] formed on the device (one launch, wl_bc_vec_terms)"""
+    K, Fp, bp = _term_args(F, b)
+    g = vgrid(a)
+    check(lib().wl_bc_vec_terms(ptr(a), K, Fp, bp, C.byref(g), int(bool(saveexit)), perdir_mask(perdir), stream()))
+
+
 def perBC_(a, perdir):
     """perBC!(a,perdir)   src/core.jl:239-243"""
     if not perdir:

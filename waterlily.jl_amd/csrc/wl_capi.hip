@@ -4,6 +4,7 @@
 
 #include "wl_common.hpp"
 #include "wl_mg.hpp"
+#include "wl_terms.hpp"
 
 static thread_local std::string g_err;
 void wl_set_error(const std::string& s) { g_err = s; }
@@ -131,6 +132,25 @@ int wl_bc_vec_fn(float* a, const float* Ub, const wl_grid* g, int saveexit, unsi
 int wl_meanflow_update(float* P, float* U, float* UU, const float* p, const float* u, const wl_grid* g, float eps, void* st) { GRID_ARG(g); WL_CHECK(P && U && p && u, "bad argument"); return wl::meanflow_update(P, U, UU, p, u, G, eps, wl_stream(st)); }
 int wl_meanflow_uu(float* tau, const float* UU, const float* U, const wl_grid* g, void* st) { GRID_ARG(g); WL_CHECK(tau && UU && U, "bad argument"); return wl::meanflow_uu(tau, UU, U, G, wl_stream(st)); }
 int wl_accelerate_field(float* r, const float* gfield, const wl_grid* g, void* st) { GRID_ARG(g); WL_CHECK(r && gfield, "bad argument"); return wl::add_field(r, gfield, (size_t)G.cs * (size_t)G.D, wl_stream(st)); }
+// separable terms (wl_terms.hip): every refusal on the host, before the launch
+static int terms_leaf_ok(const char* who, const float* out, int K, const float* const* F, const float* c) {
+  if (!out || !F || !c) { wl_set_error(std::string(who) + ": null argument"); return WL_EINVAL; }
+  if (K < 1 || K > wl::TERMS_MAX) { wl_set_error(std::string(who) + ": K outside 1 ... 4"); return WL_EINVAL; }
+  for (int k = 0; k < K; k++) {
+    if (!F[k]) { wl_set_error(std::string(who) + ": a NULL field"); return WL_EINVAL; }
+    if (F[k] == out) { wl_set_error(std::string(who) + ": a field is the output array"); return WL_EINVAL; }
+    if (!std::isfinite(c[k])) { wl_set_error(std::string(who) + ": a non-finite coefficient"); return WL_EINVAL; }
+  }
+  return 0;
+}
+int wl_accel_terms(float* r, int K, const float* const* F, const float* host_c, const wl_grid* g, void* st) {
+  GRID_ARG(g); WL_TRY(terms_leaf_ok("wl_accel_terms", r, K, F, host_c));
+  return wl::accel_terms(r, K, F, host_c, (size_t)G.cs * (size_t)G.D, wl_stream(st));
+}
+int wl_bc_vec_terms(float* a, int K, const float* const* F, const float* host_b, const wl_grid* g, int saveexit, unsigned per, void* st) {
+  GRID_ARG(g); WL_TRY(terms_leaf_ok("wl_bc_vec_terms", a, K, F, host_b));
+  return wl::bc_vec_terms(a, K, F, host_b, G, saveexit, per, wl_stream(st));
+}
 int wl_bc_per_scalar(float* a, const wl_grid* g, unsigned per, void* st) { GRID_ARG(g); return wl::bc_per_scalar(a, G, per, wl_stream(st)); }
 int wl_conv_diff(float* r, const float* u, float* Phi, const wl_grid* g, float nu, unsigned per, int scheme, void* st) { GRID_ARG(g); return wl::conv_diff(r, u, Phi, G, nu, per, scheme, wl_stream(st)); }
 int wl_bdim(float* u, const float* u0, float* f, const float* V, const float* mu0, const float* mu1, const wl_grid* g, float dt, float pre, float post, void* st) {

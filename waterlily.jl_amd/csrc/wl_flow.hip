@@ -9,6 +9,7 @@
 #include "wl_common.hpp"
 #include "wl_pdefer.hpp"
 #include "wl_bcfold.hpp"
+#include "wl_bc_chain.hpp"
 #include "wl_conv_cell.hpp"
 
 namespace {
@@ -220,7 +221,7 @@ __global__ void k_conv_q1(GridX g, float* __restrict__ Phi, const float* __restr
 }
 
 // accelerate!(r,t,g,U) for accelerations that are uniform in space: r[I,i] += a_i on ALL cells   src/Flow.jl:69-73
-// (the host evaluates g(i,t)+dU(i,t)/dt; position-dependent g/uBC are not a device path)
+// (the host evaluates g(i,t)+dU(i,t)/dt; position-dependent g/uBC in separable form: k_accel_terms, wl_terms.hip)
 __global__ void k_accelerate(float* __restrict__ r, long cs, long n, float a0, float a1, float a2) {
   for (long q = (long)blockIdx.x * WL_BLOCK + threadIdx.x; q < n; q += (long)gridDim.x * WL_BLOCK) {
     const int c = (int)(q / cs);
@@ -445,16 +446,6 @@ __global__ void k_cfl(GridX g, const float* __restrict__ u, float* __restrict__ 
 // LAST direction j that touches it, fed from a source already processed by the lower directions.  resolve()
 // walks j = D..1 accordingly; the final source cell lies on no BC plane, so nothing it reads is written here.
 template <int D>
-__device__ __forceinline__ bool bc_touched(const int* I, const int* N, int a, int saveexit, unsigned per) {
-  for (int b = 0; b < D; b++) {
-    const bool pb = (per >> b) & 1u;
-    if (pb) { if (I[b] == 1 || I[b] == N[b]) return true; }
-    else if (a == b) { if (I[b] == 1 || I[b] == 2 || (I[b] == N[b] && !(saveexit && a == 0))) return true; }
-    else { if (I[b] == 1 || I[b] == N[b]) return true; }
-  }
-  return false;
-}
-template <int D>
 __global__ void k_bc_vec(GridX g, float* __restrict__ a_, float U0, float U1, float U2, int saveexit, unsigned per, int zwalls) {
   // pz = plane id: dir d = id/3, which = id%3 -> Julia index {1,2,N_d}
   const int pid = blockIdx.y, d = pid / 3, which = pid % 3;
@@ -508,46 +499,7 @@ __global__ void k_bc_vec(GridX g, float* __restrict__ a_, float U0, float U1, fl
 // (as in k_bc_vec) and then evaluated from its innermost cell outwards — the order in which the reference produces the values.
 template <int D>
 __global__ void k_bc_vec_fn(GridX g, float* __restrict__ a_, const float* __restrict__ Ub, int saveexit, unsigned per, int zwalls) {
-  const int pid = blockIdx.y, d = pid / 3, which = pid % 3;
-  const int N[3] = {g.nx, g.ny, (D == 3) ? g.gnz : 1};
-  const int d1 = (d == 0) ? 1 : 0, d2 = (d == 2) ? 1 : 2;
-  const int n1 = (d1 == 0) ? g.nx : g.ny;
-  const long cnt = (long)n1 * ((D == 3) ? ((d2 == 1) ? g.ny : g.nz) : 1);
-  const long q = (long)blockIdx.x * WL_BLOCK + threadIdx.x;
-  if (q >= cnt) return;
-  int loc[3] = {0, 0, 0};
-  loc[d1] = (int)(q % n1);
-  if (D == 3) loc[d2] = (int)(q / n1);
-  const int Id = (which == 0) ? 1 : (which == 1 ? 2 : N[d]);
-  int I[3];
-  if (d == 2) { const int kl = Id - 1 - g.gk; if (kl < 0 || kl >= g.nz) return; loc[2] = kl; if (!zwalls) return; }
-  else loc[d] = Id - 1;
-  I[0] = loc[0] + 1; I[1] = loc[1] + 1; I[2] = (D == 3) ? g.gk + loc[2] + 1 : 1;
-  if (D == 3 && d != 2) {
-    const int K = I[2];
-    const bool owned = (loc[2] >= g.k0 && loc[2] < g.k1) || (zwalls && (K == 1 || K == N[2]));   // (z-periodic slabs: planes 1 and N are halo planes too)
-    if (!owned) return;
-  }
-  auto off = [&](const int* J) -> long { return (long)(J[0] - 1) + (long)(J[1] - 1) * g.sy + ((D == 3) ? (long)(J[2] - 1 - g.gk) * g.sz : 0); };
-  for (int a = 0; a < D; a++) {
-    if (!bc_touched<D>(I, N, a, saveexit, per)) continue;
-    long chain[4]; bool neu[4]; int nc = 0;        // cells from I inwards; neu[q]: step q→q+1 is a Neumann (function) step, else a periodic copy
-    int J[3] = {I[0], I[1], I[2]};
-    chain[0] = off(J);
-    bool dirichlet = false;
-    for (int b = D - 1; b >= 0; b--) {
-      const bool pb = (per >> b) & 1u;
-      int moved = 0;
-      if (pb) { if (J[b] == 1) { J[b] = N[b] - 1; moved = 1; } else if (J[b] == N[b]) { J[b] = 2; moved = 1; } }
-      else if (a == b) { if (J[b] == 1 || J[b] == 2 || (J[b] == N[b] && !(saveexit && a == 0))) { dirichlet = true; break; } }
-      else { if (J[b] == 1) { J[b] = 2; moved = 2; } else if (J[b] == N[b]) { J[b] = N[b] - 1; moved = 2; } }
-      if (moved) { neu[nc] = moved == 2; nc++; chain[nc] = off(J); }
-    }
-    const float* __restrict__ Ua = Ub + (long)a * g.cs;
-    float v = dirichlet ? Ua[chain[nc]] : a_[(long)a * g.cs + chain[nc]];
-    for (int qk = nc - 1; qk >= 0; qk--) if (neu[qk]) v = (Ua[chain[qk]] + v) - Ua[chain[qk + 1]];
-    a_[(long)a * g.cs + chain[0]] = v;
-  }
+  bc_vec_chain<D>(g, a_, BcTableSrc{Ub}, saveexit, per, zwalls);      // (wl_bc_chain.hpp: shared with k_bc_vec_terms, wl_terms.hip)
 }
 // MeanFlow update!  src/Metrics.jl:236-248:  P = ε·p + (1−ε)·P ;  U = ε·u + (1−ε)·U ;  UU[I,i,j] = ε·(u[I,i]·u[I,j]) + (1−ε)·UU[I,i,j]  (all cells)
 __global__ void k_meanflow(float* __restrict__ P, float* __restrict__ U, float* __restrict__ UU, const float* __restrict__ p, const float* __restrict__ u, long cs, int D, float e) {
@@ -678,12 +630,7 @@ int bc_vec(float* a, const GridX& g, const float* U, int saveexit, unsigned per,
   WL_LAUNCH_CHECK(); return 0;
 }
 int bc_vec_fn(float* a, const float* Ub, const GridX& g, int saveexit, unsigned per, hipStream_t s) {
-  long cmax = (long)g.ny * (g.D == 3 ? g.nz : 1);
-  cmax = cmax > (long)g.nx * (g.D == 3 ? g.nz : 1) ? cmax : (long)g.nx * (g.D == 3 ? g.nz : 1);
-  cmax = cmax > g.sz ? cmax : g.sz;
-  const bool dist = (g.D == 3) && (g.nz != g.gnz);
-  const int zwalls = (g.D == 3) ? ((dist && ((per >> 2) & 1u)) ? 0 : 1) : 0;
-  dim3 grid((unsigned)((cmax + WL_BLOCK - 1) / WL_BLOCK), (unsigned)(3 * g.D), 1);
+  int zwalls; const dim3 grid = bc_chain_grid(g, per, &zwalls);
   DSEL(g.D, k_bc_vec_fn, grid, dim3(WL_BLOCK), 0, s, g, a, Ub, saveexit, per, zwalls);
   WL_LAUNCH_CHECK(); return 0;
 }

@@ -15,6 +15,7 @@
 #include "wl_forces.hpp"
 #include "wl_meanflow.hpp"
 #include "wl_observe.hpp"
+#include "wl_terms.hpp"
 
 namespace {
 // apply!(u0,u): u[I,i] = u0(i, loc(i,I))   src/Flow.jl:81-83, loc src/core.jl:177 (Float32)
@@ -78,7 +79,8 @@ struct wl_sim {
   float* ps = nullptr;       // spare pressure array (out-of-place x·dt and x/dt around the solve; two swaps restore p's identity)
   bool use_fuse_p = true;
   double* exit_sc = nullptr; // exitBC! on slabs: global face means (device)
-  bool forcing = false;      // uniform g(i,t)+dU(i,t)/dt supplied by the host for the current step (accelerate!, src/Flow.jl:69-73)
+  bool forcing = false;      // the host supplies g+dU/dt or boundary values for the current step — uniform (acc_uniform) or as separable terms (terms_on()): the staged sequence
+  bool acc_uniform = false;  // uniform g(i,t)+dU(i,t)/dt (wl_sim_set_forcing; accelerate!, src/Flow.jl:69-73)
   float acc0[3] = {0, 0, 0}, acc1[3] = {0, 0, 0};   // at t₀ (predictor) and t₁ (corrector)
   float* us = nullptr;       // spare velocity array: the fused corrector writes here, then u and us trade places
   // sgs! as the step's udf (wl_sim_set_sgs; src/Flow.jl:191-193,206-208 with udf=sgs!, src/util.jl:66-76): the model adds to r = conv_diff!'s output, so both
@@ -87,6 +89,26 @@ struct wl_sim {
   int sgs_model = 0;         // 0 off, 1 Smagorinsky–Lilly
   float sgs_Cs = 0.f, sgs_Delta = 1.f;
   int sgs_udf(const float* uadv, hipStream_t s) { return sgs_model ? wl::sgs(f, sigma, uadv, G, sgs_Cs, sgs_Delta, s) : 0; }   // udf!(a,sgs!,uadv,t)
+  // separable terms (wl_sim_set_terms, wl_terms.hip): uBC(i,x,t) = Σₖ bₖ(t)·Fₖ and g + ∂ₜuBC = Σₖ aₖ(t)·Fₖ with K handle-owned fields of the shape of u and the
+  // coefficients the host left in force (wl_sim_set_term_coeffs).  Acceleration coefficients: the staged sequence, like `forcing`; boundary coefficients: every
+  // BC!(u) is k_bc_vec_terms and nothing folds or defers it (fold_ok) — the projection tails get no tuple U
+  int tK = 0;
+  float* tmem = nullptr;                          // K·cs·D floats
+  const float* tF[wl::TERMS_MAX] = {nullptr, nullptr, nullptr, nullptr};
+  bool t_acc = false, t_bc = false;
+  float tacc0[wl::TERMS_MAX] = {0, 0, 0, 0}, tacc1[wl::TERMS_MAX] = {0, 0, 0, 0}, tb1[wl::TERMS_MAX] = {0, 0, 0, 0};   // aₖ(t₀), aₖ(t₁), bₖ(t₁)
+  long n_term_accel = 0, n_term_bc = 0;           // launches of the two kernels (wl_sim_counter "term_accel", "term_bc")
+  bool terms_on() const { return t_acc || t_bc; }
+  void forcing_changed() { forcing = acc_uniform || terms_on(); }      // everything that stands down for `forcing` stands down for terms of either kind
+  int accel_terms(const float* c, hipStream_t s) {      // accelerate!(f,t,g,uBC) from the terms, behind the uniform launch
+    if (!t_acc) return 0;
+    n_term_accel++;
+    return wl::accel_terms(f, tK, tF, c, (size_t)G.cs * (size_t)d.D, s);
+  }
+  int bc_launch(hipStream_t s) {                        // BC!(u,uBC,exitBC,perdir,t₁): the tuple, or the terms with the coefficients in force
+    if (t_bc) { n_term_bc++; return wl::bc_vec_terms(u, tK, tF, tb1, G, d.exitBC, d.perdir_mask, s); }
+    return wl::bc_vec(u, G, d.uBC, d.exitBC, d.perdir_mask, s);
+  }
   bool fused_nobody_conv() const { return us && !d.has_body && !forcing && !sgs_model; }   // predict/correct run conv_diff!+BDIM! as one launch (the NoBody form; `us`: the corrector writes out of place)
   std::vector<float> dt;
   bool own_mg = true;        // false: the multigrid handle belongs to the caller (wl_sim_create_on)
@@ -103,7 +125,7 @@ struct wl_sim {
   // makes memory current for a reader outside the step (fields handed out, force read-outs, wl_sim_phase, a failed step).  Between calls nothing is pending but, on
   // slabs, the exchange — "a call never returns with the divisor pending", every projection ends with BC! applied — so this launches nothing there.
   int settle(hipStream_t s) { WL_TRY(sync_u(s)); WL_TRY(materialise_p(s)); return flush_bc(s); }
-  ~wl_sim() { if (df.u_pending && comm && comm->cs) (void)hipStreamSynchronize(comm->cs); if (own_mg) delete mg; if (own) (void)hipFree(own); if (exit_sc) (void)hipFree(exit_sc); if (farmask) (void)hipFree(farmask); if (mnear) (void)hipFree(mnear); if (mneedf) (void)hipFree(mneedf); if (mm0var) (void)hipFree(mm0var); }
+  ~wl_sim() { if (df.u_pending && comm && comm->cs) (void)hipStreamSynchronize(comm->cs); if (own_mg) delete mg; if (own) (void)hipFree(own); if (exit_sc) (void)hipFree(exit_sc); if (farmask) (void)hipFree(farmask); if (mnear) (void)hipFree(mnear); if (mneedf) (void)hipFree(mneedf); if (mm0var) (void)hipFree(mm0var); if (tmem) (void)hipFree(tmem); }
 
   // BC!(u) on the physical faces this rank holds, then the z-halo planes (depth 2: QUICK reads f[I-2δ], src/Flow.jl:8)
   // On slabs the exchange runs on the communicator's own stream; the compute stream waits for it (sync_u) only where the halo
@@ -114,11 +136,11 @@ struct wl_sim {
   // measured at 512³: projection tails −0.04 ms/step (kept), tiled conv_diff! +0.2…0.4 ms/step — the ghost writes are sector-granular
   // wherever they happen, and inside the tiled kernel they sit on the wall tiles' critical path (off; `bcfold` = 3 turns it on)
   int use_bcfold = 1;         // bit 0: projection tails, bit 1: tiled conv_diff!+BDIM!
-  bool fold_ok(int bit) const { return (use_bcfold & bit) && !comm && !d.exitBC && !d.perdir_mask && wl_bc_fold_geom_ok(G); }
+  bool fold_ok(int bit) const { return (use_bcfold & bit) && !comm && !d.exitBC && !d.perdir_mask && !t_bc && wl_bc_fold_geom_ok(G); }
   int bc_u(hipStream_t s) {
     WL_TRY(sync_u(s));
     if (df.bc_folded) { df.bc_folded = false; return 0; }      // the producer already wrote every boundary location
-    WL_TRY(wl::bc_vec(u, G, d.uBC, d.exitBC, d.perdir_mask, s));
+    WL_TRY(bc_launch(s));
     if (comm && use_overlap) { WL_TRY(wl::halo_async_begin(comm, u, G, d.D, 2, s)); df.u_pending = true; return 0; }
     return wl::halo(comm, u, G, d.D, 2, s);
   }
@@ -237,7 +259,7 @@ struct wl_sim {
   int flush_bc(hipStream_t s) {       // apply a deferred BC! now (somebody is about to read u's boundary locations from memory)
     if (!df.bc_deferred) return 0;
     df.bc_deferred = false;
-    return wl::bc_vec(u, G, d.uBC, d.exitBC, d.perdir_mask, s);
+    return bc_launch(s);
   }
   int predict(hipStream_t s, const float* dt_dev = nullptr) {                            // mom_predict! src/Flow.jl:190-196 (dt_dev: Δt still on the device — lazydt_ok() paths only)
     if (hybrid_ok()) {
@@ -255,7 +277,8 @@ struct wl_sim {
     } else {
       { ProfScope pc(WL_PROF_CONVDIFF, s); WL_TRY(conv_only(u0, s)); }
       WL_TRY(sgs_udf(u0, s));                                                              // udf!(a,udf,a.u⁰,t₀): the model sees u⁰ (a.u is zeroed)
-      if (forcing) WL_TRY(wl::accelerate(f, G, acc0, s));                                  // accelerate!(f,t₀,g,uBC)
+      if (acc_uniform) WL_TRY(wl::accelerate(f, G, acc0, s));                                  // accelerate!(f,t₀,g,uBC)
+      WL_TRY(accel_terms(tacc0, s));                                                       // … its position-dependent part
       WL_TRY(bdim_step(0.f, 1.f, s));   // scale_u!(a,0) folded (pre=0)
     }
     WL_TRY(fused_conv ? bc_u_or_defer(false, s) : bc_u(s));      // (deferral implies !exitBC: fold_ok)
@@ -282,7 +305,8 @@ struct wl_sim {
     }
     { ProfScope pc(WL_PROF_CONVDIFF, s); WL_TRY(conv_only(u, s)); }
     WL_TRY(sgs_udf(u, s));                                                                 // udf!(a,udf,a.u,t): the model sees the projected u
-    if (forcing) WL_TRY(wl::accelerate(f, G, acc1, s));                                    // accelerate!(f,t₁,g,uBC)
+    if (acc_uniform) WL_TRY(wl::accelerate(f, G, acc1, s));                                    // accelerate!(f,t₁,g,uBC)
+    WL_TRY(accel_terms(tacc1, s));
     WL_TRY(bdim_step(1.f, 0.5f, s));  // scale_u!(a,0.5) folded (post)
     return bc_u(s);
   }
@@ -848,6 +872,8 @@ int wl_sim_counter(wl_sim* s, const char* name, long* out) {
   if (n == "part") { *out = s->mg->lv[0].part ? 1 : 0; return 0; }                 // the finest level's z-split: decided / planes [za, zb] off the constant pattern
   if (n == "part_za") { *out = s->mg->lv[0].za; return 0; }
   if (n == "part_zb") { *out = s->mg->lv[0].zb; return 0; }
+  if (n == "term_accel") { *out = s->n_term_accel; return 0; }                     // launches of k_accel_terms / k_bc_vec_terms by this handle (wl_sim_set_terms)
+  if (n == "term_bc") { *out = s->n_term_bc; return 0; }
   if (n == "launches") { *out = s->n_step_launches; return 0; }                    // kernel launches of this handle's mom_step! calls so far
   if (n == "probe_records") { *out = s->obs.probes.n; return 0; }                       // probe records held / refused by a full buffer
   if (n == "probe_dropped") { *out = s->obs.probes.dropped; return 0; }
@@ -861,8 +887,49 @@ int wl_sim_counter(wl_sim* s, const char* name, long* out) {
 int wl_sim_set_forcing(wl_sim* s, const float* U1, const float* a0, const float* a1) {
   const int D = s->d.D;
   if (U1) for (int c = 0; c < D; c++) s->d.uBC[c] = U1[c];
-  s->forcing = a0 != nullptr || a1 != nullptr;
+  s->acc_uniform = a0 != nullptr || a1 != nullptr; s->forcing_changed();
   for (int c = 0; c < 3; c++) { s->acc0[c] = (a0 && c < D) ? a0[c] : 0.f; s->acc1[c] = (a1 && c < D) ? a1[c] : 0.f; }
+  return 0;
+}
+// separable terms (wlhip.h): every refusal is decided on the host, before any launch or allocation
+int wl_sim_set_terms(wl_sim* s, int K, const float* const* host_F, void* st) {
+  WL_CHECK(s, "null wl_sim");
+  if (s->comm) { wl_set_error("wl_sim_set_terms: z-slab handles are not supported (single domain only)"); return WL_EINVAL; }
+  if (K < 0 || K > wl::TERMS_MAX) { wl_set_error("wl_sim_set_terms: K outside 0 ... 4"); return WL_EINVAL; }
+  const size_t n = (size_t)s->G.cs * (size_t)s->d.D;
+  if (K > 0) {
+    if (!host_F) { wl_set_error("wl_sim_set_terms: a NULL field"); return WL_EINVAL; }
+    for (int k = 0; k < K; k++) {
+      if (!host_F[k]) { wl_set_error("wl_sim_set_terms: a NULL field"); return WL_EINVAL; }
+      for (size_t q = 0; q < n; q++) if (!std::isfinite(host_F[k][q])) { wl_set_error("wl_sim_set_terms: a non-finite value in a field"); return WL_EINVAL; }
+    }
+  }
+  hipStream_t q = wl_stream(st);
+  WL_TRY(s->settle(q));
+  if (s->tmem) { WL_HIP(hipStreamSynchronize(q)); WL_HIP(hipFree(s->tmem)); s->tmem = nullptr; }      // (hipFree waits for every stream that may still read the old fields)
+  s->tK = 0; s->t_acc = s->t_bc = false; s->forcing_changed();
+  for (int k = 0; k < wl::TERMS_MAX; k++) { s->tF[k] = nullptr; s->tacc0[k] = s->tacc1[k] = s->tb1[k] = 0.f; }
+  if (K == 0) return 0;
+  WL_HIP(hipMalloc((void**)&s->tmem, sizeof(float) * n * (size_t)K));
+  for (int k = 0; k < K; k++) {
+    s->tF[k] = s->tmem + n * (size_t)k;
+    WL_HIP(hipMemcpyAsync(s->tmem + n * (size_t)k, host_F[k], sizeof(float) * n, hipMemcpyHostToDevice, q));
+  }
+  WL_HIP(hipStreamSynchronize(q));      // the host arrays are the caller's again
+  s->tK = K;
+  return 0;
+}
+float* wl_sim_term(wl_sim* s, int k) { return (s && k >= 0 && k < s->tK) ? s->tmem + (size_t)s->G.cs * (size_t)s->d.D * (size_t)k : nullptr; }
+int wl_sim_set_term_coeffs(wl_sim* s, const float* acc0, const float* acc1, const float* bc1) {
+  WL_CHECK(s, "null wl_sim");
+  if (s->comm) { wl_set_error("wl_sim_set_term_coeffs: z-slab handles are not supported (single domain only)"); return WL_EINVAL; }
+  if (s->tK == 0 && (acc0 || acc1 || bc1)) { wl_set_error("wl_sim_set_term_coeffs: coefficients given while K = 0 (wl_sim_set_terms)"); return WL_EINVAL; }
+  for (const float* c : {acc0, acc1, bc1}) if (c) for (int k = 0; k < s->tK; k++) if (!std::isfinite(c[k])) { wl_set_error("wl_sim_set_term_coeffs: a non-finite coefficient"); return WL_EINVAL; }
+  s->t_acc = acc0 != nullptr || acc1 != nullptr;
+  s->t_bc = bc1 != nullptr; s->forcing_changed();
+  for (int k = 0; k < wl::TERMS_MAX; k++) {
+    s->tacc0[k] = (acc0 && k < s->tK) ? acc0[k] : 0.f; s->tacc1[k] = (acc1 && k < s->tK) ? acc1[k] : 0.f; s->tb1[k] = (bc1 && k < s->tK) ? bc1[k] : 0.f;
+  }
   return 0;
 }
 int wl_sim_set_sgs(wl_sim* s, int model, float Cs, float Delta) {

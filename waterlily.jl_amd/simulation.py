@@ -235,10 +235,17 @@ class FusedSimulation:
     as a fixed sequence of fused HIP kernels on one stream.  This is what bench.py times."""
 
     def __init__(self, dims, uBC, L, U=None, dt=0.25, nu=0.0, perdir=(), exitBC=False, lam=core.QUICK, has_body=False, ic="uBC", u0=None,
-                 g=None, duBC_dt=None):
+                 g=None, duBC_dt=None, terms=None, g_t=None, b_t=None, db_t=None):
         """uBC: tuple, or a function uBC(i,t) that is uniform in space (i = 1..D as in the reference) together with its time
         derivative duBC_dt(i,t) (the reference differentiates it with ForwardDiff, src/Flow.jl:72-73); g: body force g(i,t),
-        uniform in space.  Position-dependent uBC/g are not a device path."""
+        uniform in space.
+
+        Position-dependent uBC(i,x,t) and g(i,x,t) in separable form (include/wlhip.h, separable terms):
+            uBC(i,x,t) = Σₖ b_t(t)[k]·terms[k][I,i]      g(i,x,t) = Σₖ g_t(t)[k]·terms[k][I,i]      K = len(terms) ≤ 4
+        terms: K arrays of shape Ng + (D,) holding the spatial factors at loc(i,I) (core.tabulate(fn, dims) makes one); g_t, b_t and db_t (the time
+        derivative of b_t: accelerate! adds g + ∂ₜuBC) are each None, K constants, or a callable t -> K floats.  With b_t given every BC!(u) takes its
+        values from the terms, and with u0=None the initial field is Σₖ b_t(0)[k]·terms[k] (the reference's u0 = uBC at t = 0).  `uBC` is then only the
+        tuple the handle is created with and `U` the velocity scale."""
         core.device()
         D = len(dims)
         self._ufn = uBC if callable(uBC) else None
@@ -263,6 +270,14 @@ class FusedSimulation:
         self._h = h
         self.nu = float(nu)
         self.has_body = bool(has_body)
+        self._tK, self._tcoef, self._tdyn = 0, (None, None, None), False
+        if terms is not None:
+            self.set_terms(terms, g_t=g_t, b_t=b_t, db_t=db_t)
+        else:
+            assert g_t is None and b_t is None and db_t is None, "g_t, b_t and db_t are the coefficients of `terms`"
+        if u0 is None and ic == "uBC" and self._tcoef[1] is not None:      # u0 = uBC(i,x,0)   src/WaterLily.jl:100
+            u0 = self._combine(self._terms_host, self._coef(self._tcoef[1], 0.0))
+        self._terms_host = None      # (the handle owns the device copies; the host arrays were needed for the initial field only)
         if u0 is not None:
             self.set_field("u", np.asfortranarray(u0, dtype=np.float32))
         else:
@@ -297,14 +312,81 @@ class FusedSimulation:
         check(lib().wl_h2d(lib().wl_sim_field(self._h, name.encode()), a.ctypes.data_as(C.c_void_p), a.nbytes, stream()))
         check(lib().wl_stream_sync(stream()))
 
+    @staticmethod
+    def _combine(F, c):
+        """Σₖ c[k]·F[k] in Float32 in the order of the device kernels: s = c₀·F₀ ; s = s + cₖ·Fₖ"""
+        s = np.float32(c[0]) * F[0]
+        for k in range(1, len(F)):
+            s = s + np.float32(c[k]) * F[k]
+        return np.asfortranarray(s, dtype=np.float32)
+
+    def _coef(self, c, t):
+        """K coefficients at time t: constants, or a callable t -> K floats"""
+        v = c(float(t)) if callable(c) else c
+        v = [float(x) for x in v]
+        if len(v) != self._tK:
+            raise ValueError(f"{len(v)} coefficients for {self._tK} terms")
+        return v
+
+    def set_terms(self, terms, g_t=None, b_t=None, db_t=None):
+        """register (or, with terms=None, remove) the separable terms and their coefficients — see __init__.  Constant coefficients are handed to the
+        handle once and stay in force; callables are evaluated by the host before every step."""
+        K = 0 if terms is None else len(terms)
+        host = [np.asfortranarray(f, dtype=np.float32) for f in (terms or [])]
+        for f in host:
+            if f.shape != self.Ng + (self.D,):
+                raise ValueError(f"a term has shape {f.shape}, the flow's velocity has {self.Ng + (self.D,)}")
+        Fp = (C.c_void_p * max(K, 1))(*[f.ctypes.data_as(C.c_void_p) for f in host])
+        check(lib().wl_sim_set_terms(self._h, K, Fp, stream()))
+        self._tK, self._terms_host = K, host
+        self._tcoef = (g_t, b_t, db_t)
+        self._tdyn = any(callable(c) for c in self._tcoef)
+        if K == 0:
+            if any(c is not None for c in self._tcoef):
+                raise ValueError("coefficients without terms")
+            return
+        self._term_coeffs(0.0, 0.0)      # in force for init_flow; the constant ones for good
+
+    def term(self, k):
+        """term k as a device array over the handle's memory (for callers that fill it on the device)"""
+        import torch
+        p = lib().wl_sim_term(self._h, int(k))
+        if not p:
+            raise KeyError(k)
+        shape = self.Ng + (self.D,)
+        n, addr = int(np.prod(shape)), int(p)
+
+        class _Mem:      # __cuda_array_interface__ of memory the handle owns
+            __cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (addr, False), "version": 2}
+        t = torch.as_tensor(_Mem(), device=core.device())
+        return t.view(tuple(reversed(shape))).permute(*reversed(range(len(shape))))
+
+    def _term_coeffs(self, t0, t1):
+        """aₖ(t₀), aₖ(t₁) = gₖ + bₖ′ and bₖ(t₁) into the handle (wl_sim_set_term_coeffs)"""
+        g_t, b_t, db_t = self._tcoef
+        K = self._tK
+        arr = lambda v: (C.c_float * K)(*v)      # noqa: E731
+        acc = None
+        if g_t is not None or (b_t is not None and db_t is not None):
+            def acc(t):
+                gv = self._coef(g_t, t) if g_t is not None else [0.0] * K
+                dv = self._coef(db_t, t) if (b_t is not None and db_t is not None) else [0.0] * K
+                return arr([a + b for a, b in zip(gv, dv)])
+        check(lib().wl_sim_set_term_coeffs(self._h, acc(t0) if acc else None, acc(t1) if acc else None,
+                                           arr(self._coef(b_t, t1)) if b_t is not None else None))
+
     def _forcing(self):
         """uBC(i,t₁) and g(i,t)+dU(i,t)/dt at t₀, t₁ for the coming step (mom_step!, src/Flow.jl:157; accelerate! :69-73)"""
-        if self._ufn is None and self._gfn is None:
+        if self._ufn is None and self._gfn is None and not self._tdyn:
             return
         D = self.D
         dtl = np.float32(lib().wl_sim_dt_last(self._h))
         t1 = np.float32(np.float32(lib().wl_sim_time(self._h)) + dtl)      # t₁ = sum(Δt) ; t₀ = t₁ - Δt[end]   src/Flow.jl:157
         t0 = np.float32(t1 - dtl)
+        if self._tdyn:
+            self._term_coeffs(t0, t1)
+        if self._ufn is None and self._gfn is None:
+            return
         arr = lambda v: (C.c_float * 3)(*([float(x) for x in v] + [0.0] * (3 - D)))
         U1 = arr([self._ufn(i + 1, float(t1)) for i in range(D)]) if self._ufn is not None else None
         acc = lambda t: arr([(self._gfn(i + 1, float(t)) if self._gfn else 0.0) + (self._dufn(i + 1, float(t)) if (self._ufn and self._dufn) else 0.0) for i in range(D)])
@@ -316,7 +398,7 @@ class FusedSimulation:
 
     def mom_steps_(self, n):
         """n × mom_step! in one library call (no time-dependent uBC / g between the steps: those are evaluated by the host per step — use mom_step_)"""
-        if self._ufn is not None or self._gfn is not None:
+        if self._ufn is not None or self._gfn is not None or self._tdyn:
             for _ in range(int(n)):
                 self.mom_step_()
             return
@@ -367,7 +449,7 @@ class FusedSimulation:
         check(lib().wl_sim_set_option(self._h, name.encode(), int(value)))
 
     def counter(self, name):
-        """path counters of the handle (include/wlhip_bench.h wl_sim_counter): "resjac", "resjac_redo", "resjac_backoff", "xdefer", "abwide", "tailfuse", "bcdefer", "pdefer", "tailwide", "rskip", "rskip_redo", "tailspec", "tailspec_armed", "launches", "probe_records", "probe_dropped", "force_records", "force_dropped", "force_tiles", "mean_updates", "mean_every"; "tailfuse_min" reads the size gate of "tailfuse" in force;
+        """path counters of the handle (include/wlhip_bench.h wl_sim_counter): "resjac", "resjac_redo", "resjac_backoff", "xdefer", "abwide", "tailfuse", "bcdefer", "pdefer", "tailwide", "rskip", "rskip_redo", "tailspec", "tailspec_armed", "launches", "probe_records", "probe_dropped", "force_records", "force_dropped", "force_tiles", "mean_updates", "mean_every", "term_accel", "term_bc"; "tailfuse_min" reads the size gate of "tailfuse" in force;
         with a body: "hybrid", "body_tile", "mask_valid", "part", "part_za", "part_zb" and the mask census "mask_near", "mask_needf_only", "mask_m0var_only",
         "mask_clean_in_box", "dirty_z0", "dirty_z1", "near_b0", "near_b1", "near_k0", "near_k1" """
         v = C.c_long(0)
